@@ -10,7 +10,11 @@ tracked but does not stop the timed work).  With --gpus N the 500k wavelengths a
 sharded over N ranks (strong scaling) with one exchange of the per-sweep partial sums (the
 engine's P2P mailboxes over xGMI by default).
 
-Run:  python bench.py [--gpus N --steps K --warmup W]
+Run:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+      A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is
+      given and prints the headline line.  --full adds every other leg (sweep-kernel roofline,
+      radiative equilibrium, per-species, chemistry, provider, CPU baselines, K6 binning, C5),
+      each with runs of its own after the timed steps; the --no-* options trim that set.
       (N > 1 either under a launcher — python -m torch.distributed.run --nproc-per-node N
       bench.py --gpus N ... — or on its own: without WORLD_SIZE in the environment the process
       starts N rank processes of itself (launch_ranks) before anything touches the GPU and prints
@@ -51,6 +55,15 @@ def parse():
     ap.add_argument("--n-lam", type=int, default=500_000)
     ap.add_argument("--n-layers", type=int, default=60)
     ap.add_argument("--n-T", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (sweep-kernel roofline, "
+                         "radiative equilibrium, per-species, chemistry, provider, CPU baselines, "
+                         "K6 binning, C5) and report them in the result line; the options below "
+                         "that skip or size a leg apply to this mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what their last step left on rank 0's "
+                         "engine (temperatures, emergent spectrum, a fixed seeded sample of the "
+                         "flux columns) as DIR/<name>.npy, float64")
     ap.add_argument("--rad-eq-max", type=int, default=200,
                     help="max T-P iterations for the iterations-to-radiative-equilibrium run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -481,6 +494,32 @@ def build_engine_fallback(w, tabs, lo, hi, d, force, note):
             note + f"; RCCL setup failed too ({err or 'on a peer rank'}): host all-gather")
 
 
+DUMP_SEED = 20240607
+DUMP_FLUX_BYTES = 40 << 20      # both sampled flux arrays together
+DUMP_SPECTRUM_BYTES = 16 << 20  # a longer spectrum is sampled at the same columns
+
+
+def dump_outputs(eng, out_dir):
+    """What the timed steps left on this engine, as the caller of state_init + iterate reads it
+    back: the layer temperatures, the emergent spectrum F_up[-1] and the up and down fluxes of
+    every layer.  The fluxes (n_layers x n_lam each) are written at a fixed, seeded sample of
+    wavelength columns, so that the files stay below 64 MB in all (the default workload: 16384
+    of 500k columns, 20 MB).  Written as out_dir/<name>.npy, float64; returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    nL, n = eng.n_layers, eng.n_lam
+    n_cols = int(min(n, 16384, DUMP_FLUX_BYTES // (2 * 8 * nL)))
+    cols = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=n_cols, replace=False))
+    up, down = eng.get_fluxes()
+    spec = eng.get_spectrum()
+    arrays = {"temperatures": eng.get_temperatures(),
+              "spectrum": spec if spec.nbytes <= DUMP_SPECTRUM_BYTES else spec[cols],
+              "flux_up_sample": up[:, cols], "flux_down_sample": down[:, cols],
+              "sample_columns": cols.astype(np.float64)}
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    return {name: list(v.shape) for name, v in arrays.items()}
+
+
 def timed_iterations(eng, d, warmup, steps):
     """Fixed-work T-P iterations: warm-up, then exactly ``steps`` bracketed by a barrier and a
     stream synchronize on both sides; the max over ranks."""
@@ -630,6 +669,56 @@ def main():
     # ---- headline: timed fixed-work T-P iterations (no per-kernel events inside)
     eng.state_init(w["T0"])
     elapsed = timed_iterations(eng, d, a.warmup, a.steps)
+    updates_per_step = 2 * (nL - 1) * (hi - lo if a.lam_slice else n_lam)
+    value = updates_per_step * a.steps / elapsed
+    ms_per_step = elapsed / a.steps * 1e3
+    # ---- the state the last timed step left, before anything else steps the engine
+    dumped = None
+    if a.dump_outputs and d.rank == 0:
+        dumped = dump_outputs(eng, a.dump_outputs)
+
+    def headline():
+        """The result line of a plain run: the timed steps and what set them up."""
+        line = {
+            "metric": "lambda-bin*layer flux updates/sec at 60 layers x 500k lambda",
+            "value": value,
+            "unit": "updates/s",
+            "n_gpus": d.world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic (separable line-forest opacity tables generated on device)",
+            "config": {"workload": f"C3/C4: {nL} layers x {n_lam} lambda, {S} species "
+                                   f"(H2O/CO/CO2/CH4/Na/K + H2-H2/H2-He CIA), {a.n_T} T-nodes, "
+                                   "1 step = 1 T-P iteration (emit+absorb)",
+                       "n_layers": nL, "n_lambda": n_lam, "n_species": S, "n_T": a.n_T,
+                       "parallelism": f"lambda-shard x{d.world}"
+                                      + ("" if d.world == 1 and not a.force_comm
+                                         else f" ({kind} exchange per sweep)"),
+                       "slicing": slicing},
+            "tp_iters_per_s": 1e3 / ms_per_step,
+            "sweep_path": dict(path, setup_ms=setup_ms, setup_phases_ms=setup_phases,
+                               tables_s=tables_s,
+                               note="setup_ms: one-time metadata build + species contraction "
+                                    "(K3) per tables/mmr, outside the timed steps; tables_s: "
+                                    "context creation + device table generation"),
+        }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped,
+                                      "note": "rank 0's wavelength slice after the last timed "
+                                              "step; flux_*_sample: the columns listed in "
+                                              "sample_columns"}
+        return line
+
+    if not a.full:
+        eng.close()
+        if d.rank == 0:
+            _emit_result(headline())
+        return
     # ---- sweep-kernel duration: HIP events on the engine's stream around every sweep launch
     avg_sweep_ms, n_sweeps, xch_ms, n_xch = sweep_kernel_time(eng, max(2, a.steps // 2))
     exchange = None
@@ -643,9 +732,6 @@ def main():
                                           if kind == "p2p" else
                                           "stream time of the all-gather, per sweep "
                                           "(includes waiting for the slowest rank)")}
-    updates_per_step = 2 * (nL - 1) * (hi - lo if a.lam_slice else n_lam)
-    value = updates_per_step * a.steps / elapsed
-    ms_per_step = elapsed / a.steps * 1e3
 
     # ---- roofline of the dominant kernel (sweep), per launch, this rank's slice
     S_run = 1 if path["contracted"] else S    # K3 sweeps read one contracted table
@@ -800,34 +886,9 @@ def main():
     if d.rank == 0 and not a.no_binning:
         binning = binning_leg(a, d.local, cpu=(d.world == 1 and not a.no_cpu_baseline))
     if d.rank == 0:
-        line = {
-            "metric": "lambda-bin*layer flux updates/sec at 60 layers x 500k lambda",
-            "value": value,
-            "unit": "updates/s",
-            "n_gpus": d.world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (separable line-forest opacity tables generated on device)",
-            "config": {"workload": f"C3/C4: {nL} layers x {n_lam} lambda, {S} species "
-                                   f"(H2O/CO/CO2/CH4/Na/K + H2-H2/H2-He CIA), {a.n_T} T-nodes, "
-                                   "1 step = 1 T-P iteration (emit+absorb)",
-                       "n_layers": nL, "n_lambda": n_lam, "n_species": S, "n_T": a.n_T,
-                       "parallelism": f"lambda-shard x{d.world}"
-                                      + ("" if d.world == 1 and not a.force_comm
-                                         else f" ({kind} exchange per sweep)"),
-                       "slicing": slicing},
-            "tp_iters_per_s": 1e3 / ms_per_step,
+        line = headline()
+        line.update({
             "exchange": exchange,
-            "sweep_path": dict(path, setup_ms=setup_ms, setup_phases_ms=setup_phases,
-                               tables_s=tables_s,
-                               note="setup_ms: one-time metadata build + species contraction "
-                                    "(K3) per tables/mmr, outside the timed steps; tables_s: "
-                                    "context creation + device table generation"),
             "rad_eq": {"iterations": n_iter, "max_iterations": a.rad_eq_max,
                        "wall_s": rad_eq_wall, "iters_per_s": n_iter / rad_eq_wall,
                        "setup_s": setup_ms * 1e-3,
@@ -873,7 +934,7 @@ def main():
             "cpu_baseline": cpu,
             "k6_binning": binning,
             "c5_batched": c5,
-        }
+        })
         _emit_result(line)
 
 

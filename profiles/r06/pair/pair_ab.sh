@@ -7,7 +7,7 @@ O=gpurun_out/${1:-pair_ab}
 mkdir -p $O
 timeout -k 10 600 python3 -u -m pytest -x -v --timeout 200 --timeout-method thread -m gpu tests/test_gpu_tail.py > $O/tests.log 2>&1 || { echo tests failed; tail -40 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-B="python3 bench.py --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --no-provider --rad-eq-max 1 --steps 40 --warmup 5"
+B="python3 bench.py --full --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --no-provider --rad-eq-max 1 --steps 40 --warmup 5"
 export FREI_P2P_TIMEOUT_S=3
 for rep in 1 2; do
   for comm in p2p local; do

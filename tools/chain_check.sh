@@ -11,7 +11,7 @@ for ch in 0 1; do
   FREI_HIP_LIB=abv/trace.so FREI_CHAIN=$ch $T --n-lam 62500 > $O/t_ch${ch}.txt 2>&1
   echo "== chain $ch"; cat $O/t_ch${ch}.txt
 done
-B="python3 bench.py --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
+B="python3 bench.py --full --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
 for r in 1 2 3; do
   for ch in 0 1; do
     FREI_CHAIN=$ch timeout -k 10 120 $B > $O/b_ch${ch}_$r.json 2>/dev/null

@@ -9,7 +9,7 @@ tail -1 $O/pytest.txt
 T="timeout -k 10 120 python3 tools/trace_probe.py"
 FREI_HIP_LIB=abv/trace.so FREI_CHAIN=1 $T --n-lam 62500 2>/dev/null | grep -v "launch type \['update_fused'\]\|^     update_fused: first entry   0.00" > $O/t_ch1.txt; cat $O/t_ch1.txt
 FREI_HIP_LIB=abv/trace.so FREI_CHAIN=1 $T --n-lam 62500 --p2p 2>/dev/null > $O/tp_ch1.txt; cat $O/tp_ch1.txt
-B="python3 bench.py --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
+B="python3 bench.py --full --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
 for r in 1 2 3; do
   for ch in 0 1; do
     FREI_CHAIN=$ch timeout -k 10 120 $B > $O/b_ch${ch}_$r.json 2>/dev/null

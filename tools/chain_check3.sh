@@ -11,7 +11,7 @@ for w in 4 8; do
   FREI_HIP_LIB=abv/trace.so FREI_CHAIN=1 FREI_GROUP_WAVES=$w $T 2>/dev/null > $O/t_w$w.txt; echo "== waves $w"; grep -A3 "update_fused', 'chain" $O/t_w$w.txt
   FREI_HIP_LIB=abv/trace.so FREI_CHAIN=1 FREI_GROUP_WAVES=$w $T --p2p 2>/dev/null > $O/tp_w$w.txt; echo "== waves $w p2p"; grep -A3 "update_fused', 'chain" $O/tp_w$w.txt
 done
-B="python3 bench.py --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
+B="python3 bench.py --full --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
 for r in 1 2 3; do
   for cfg in "0 4" "1 4" "1 8"; do
     set -- $cfg

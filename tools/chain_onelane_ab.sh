@@ -8,7 +8,7 @@ mkdir -p $O
 timeout -k 10 300 python -u -m pytest tests/test_gpu_chain.py -x -q --timeout 200 --timeout-method thread > $O/pytest.txt 2>&1 || { tail -30 $O/pytest.txt; exit 1; }
 tail -1 $O/pytest.txt
 bash tools/pipe_rot_ab.sh ${1:-chol}_pipe
-B="python3 bench.py --steps 30 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
+B="python3 bench.py --full --steps 30 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
 for r in 1 2; do
   for cfg in "125000 0 -1" "125000 1 -1" "250000 0 -1" "250000 0 1" "250000 1 1" "500000 0 -1" "500000 0 1" "500000 1 1"; do
     set -- $cfg

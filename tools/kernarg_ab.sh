@@ -2,7 +2,7 @@
 set -o pipefail
 O=gpurun_out/karg
 mkdir -p $O
-B="python3 bench.py --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --no-provider --rad-eq-max 1 --steps 40 --warmup 5 --force-comm --lam-slice 312500:375000"
+B="python3 bench.py --full --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --no-provider --rad-eq-max 1 --steps 40 --warmup 5 --force-comm --lam-slice 312500:375000"
 for rep in 1 2; do
   for v in def 1 0; do
     if [ $v = def ]; then E=""; else E="HIP_FORCE_DEV_KERNARG=$v"; fi

@@ -4,7 +4,7 @@
 set -e -o pipefail
 O=gpurun_out/$1; A=$2; B=$3; R=${4:-3}
 mkdir -p $O
-BB="python3 bench.py --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --no-provider --rad-eq-max 1 --steps 40 --warmup 5 --force-comm --lam-slice 312500:375000"
+BB="python3 bench.py --full --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --no-provider --rad-eq-max 1 --steps 40 --warmup 5 --force-comm --lam-slice 312500:375000"
 for rep in $(seq 1 $R); do
   for lib in $A $B; do
     n=$(basename $lib .so)

@@ -4,7 +4,7 @@
 set -e -o pipefail
 O=gpurun_out/${1:-micro}
 mkdir -p $O
-B="python3 bench.py --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1"
+B="python3 bench.py --full --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1"
 for r in 1 2 3; do
   for lib in default rcp1 prio3; do
     if [ $lib = default ]; then unset FREI_HIP_LIB; else export FREI_HIP_LIB=abv/$lib.so; fi

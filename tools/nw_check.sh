@@ -13,7 +13,7 @@ for r in 1 2; do
     echo "== waves $w run $r"; cat $O/t_w${w}_$r.txt
   done
 done
-B="python3 bench.py --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
+B="python3 bench.py --full --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
 for r in 1 2; do
   for w in 4 8; do
     FREI_GROUP_WAVES=$w timeout -k 10 120 $B > $O/b_w${w}_$r.json 2>/dev/null

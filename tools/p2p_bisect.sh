@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out/p2pb
 mkdir -p $O
-B="python3 bench.py --steps 30 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --n-lam 125000 --force-comm"
+B="python3 bench.py --full --steps 30 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --n-lam 125000 --force-comm"
 for r in 1 2; do
   for v in cur prefix mbox ticks h2d; do
     lib=tools/ab_$v.so; [ $v = cur ] && lib=frei_amd/libfrei_hip.so

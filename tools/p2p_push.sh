@@ -3,7 +3,7 @@
 set -o pipefail
 O=gpurun_out/p2pp
 mkdir -p $O
-B="python3 bench.py --steps 30 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --n-lam 250000"
+B="python3 bench.py --full --steps 30 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --n-lam 250000"
 for r in 1 2 3; do
   for v in none p2p nopush; do
     lib=frei_amd/libfrei_hip.so; x="--force-comm"

@@ -4,7 +4,7 @@
 set -o pipefail
 O=gpurun_out/p2pwt
 mkdir -p $O
-B="python3 bench.py --steps 30 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1"
+B="python3 bench.py --full --steps 30 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1"
 for r in 1 2; do
   for n in 250000 125000; do
     for v in cur wt; do

@@ -6,7 +6,7 @@
 set -e -o pipefail
 O=gpurun_out/${1:-ablate}
 mkdir -p $O
-B="python3 bench.py --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --n-lam 62500 --steps 40 --warmup 5 --force-comm"
+B="python3 bench.py --full --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --n-lam 62500 --steps 40 --warmup 5 --force-comm"
 for r in 1 2; do
   for v in ${VARIANTS:-default noprod nocons pf2}; do
     unset FREI_HIP_LIB FREI_PIPE_PF

@@ -9,7 +9,7 @@ mkdir -p $O
 T="timeout -k 10 120 python3 tools/trace_probe.py --n-lam 62500"
 FREI_HIP_LIB=abv/trace.so FREI_PIPE=4 $T 2>/dev/null > $O/t_pipe_chain.txt; echo "== pipe chain"; cat $O/t_pipe_chain.txt
 FREI_HIP_LIB=abv/trace.so FREI_PIPE=4 FREI_CHAIN=0 $T 2>/dev/null > $O/t_pipe.txt; echo "== pipe"; cat $O/t_pipe.txt
-B="python3 bench.py --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
+B="python3 bench.py --full --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
 for r in 1 2 3; do
   for cfg in "0 1" "4 0" "4 1"; do
     set -- $cfg

@@ -5,7 +5,7 @@
 set -e -o pipefail
 O=gpurun_out/${1:-proj2}
 mkdir -p $O
-B="python3 bench.py --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --steps 40 --warmup 5"
+B="python3 bench.py --full --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --steps 40 --warmup 5"
 for r in 1 2; do
   timeout -k 10 200 $B > $O/bench500_$r.json 2>/dev/null
   python3 -c "import json; d=json.load(open('$O/bench500_$r.json')); print('500k one GPU', round(d['ms_per_step']*1e3,2), 'us per T-P iteration')"
@@ -16,7 +16,7 @@ import json, subprocess, sys
 n, O = int(sys.argv[1]), sys.argv[2]
 sys.path.insert(0, ".")
 from frei_amd.engine import partition, balanced_edges
-B = ["python3", "bench.py", "--no-binning", "--no-cpu-baseline", "--no-c5", "--no-per-species",
+B = ["python3", "bench.py", "--full", "--no-binning", "--no-cpu-baseline", "--no-c5", "--no-per-species",
      "--no-chemistry", "--rad-eq-max", "1", "--steps", "40", "--warmup", "5", "--force-comm"]
 def run(lo, hi, tag):
     out = subprocess.run(["timeout", "-k", "10", "150"] + B + ["--lam-slice", f"{lo}:{hi}"],

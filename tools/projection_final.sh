@@ -4,7 +4,7 @@
 set -e -o pipefail
 O=gpurun_out/${1:-projf}
 mkdir -p $O
-B="python3 bench.py --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --steps 40 --warmup 5"
+B="python3 bench.py --full --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --steps 40 --warmup 5"
 timeout -k 10 200 $B > $O/bench500.json 2>/dev/null
 python3 -c "import json; d=json.load(open('$O/bench500.json')); print('500k one GPU', round(d['ms_per_step']*1e3,2), 'us per T-P iteration')"
 for r in 0 1 2 3 4 5 6 7; do

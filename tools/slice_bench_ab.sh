@@ -5,7 +5,7 @@
 set -e -o pipefail
 O=${1:-gpurun_out/slice}
 mkdir -p $O
-B="python3 bench.py --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --force-comm"
+B="python3 bench.py --full --n-lam 62500 --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --force-comm"
 for r in 1 2 3; do
   for v in default pipe_rec q2; do
     case $v in

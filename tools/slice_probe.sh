@@ -11,7 +11,7 @@ timeout -k 10 200 python -u tools/ab_sweep.py --n-lam=62500 --rounds=7 --iters=8
 cat $O/ab_mem.txt
 for nl in 30 60 120; do
   for v in 0 4; do
-    FREI_PIPE=$v FREI_PIPE_PF=1 timeout -k 10 120 python3 bench.py --n-lam 62500 --n-layers $nl --steps 20 --rad-eq-max 1 \
+    FREI_PIPE=$v FREI_PIPE_PF=1 timeout -k 10 120 python3 bench.py --full --n-lam 62500 --n-layers $nl --steps 20 --rad-eq-max 1 \
       --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry > $O/b_${nl}_$v.json 2>/dev/null || exit $?
     python3 -c "import json; d=json.load(open('$O/b_${nl}_$v.json')); print($nl, $v, d['ms_per_step'], d['roofline']['avg_launch_ms'])"
   done

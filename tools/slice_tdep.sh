@@ -5,7 +5,7 @@
 set -e -o pipefail
 O=gpurun_out/${1:-tdep}
 mkdir -p $O
-B="python3 bench.py --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --force-comm"
+B="python3 bench.py --full --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --force-comm"
 for r in 0 7; do
   lo=$((r*62500)); hi=$(((r+1)*62500))
   for wu in 0 40; do

@@ -4,7 +4,7 @@
 set -o pipefail
 O=gpurun_out/sba
 mkdir -p $O
-B="python3 bench.py --steps 40 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --n-lam 62500 --force-comm"
+B="python3 bench.py --full --steps 40 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --rad-eq-max 1 --n-lam 62500 --force-comm"
 for r in 1 2 3; do
   for v in pipe grp; do
     env=""; [ $v = grp ] && env="FREI_PIPE=0"

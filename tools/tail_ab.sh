@@ -4,7 +4,7 @@
 set -e -o pipefail
 O=gpurun_out/${1:-tail_ab}
 mkdir -p $O
-B="python3 bench.py --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --no-provider --rad-eq-max 1 --steps 40 --warmup 5"
+B="python3 bench.py --full --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry --no-provider --rad-eq-max 1 --steps 40 --warmup 5"
 for rep in 1 2; do
   for comm in p2p local; do
     F=""; [ $comm = p2p ] && F="--force-comm"

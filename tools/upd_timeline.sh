@@ -7,7 +7,7 @@ O=${1:-gpurun_out/updt}
 N=${2:-500000}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="python3 bench.py --n-lam $N --steps 20 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
+B="python3 bench.py --full --n-lam $N --steps 20 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
 for v in full nosum nodt empty; do
   if [ $v = full ]; then unset FREI_HIP_LIB; else export FREI_HIP_LIB=abv/upd_$v.so; fi
   timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d $O/$v -o run -- $B > $O/$v.json 2>/dev/null

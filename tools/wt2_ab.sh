@@ -9,7 +9,7 @@ T="timeout -k 10 120 python3 tools/trace_probe.py --n-lam 62500"
 for lib in trace trace_wt2; do
   FREI_HIP_LIB=abv/$lib.so $T 2>/dev/null > $O/t_$lib.txt; echo "== $lib"; grep -A4 "update_fused', 'chain" $O/t_$lib.txt
 done
-B="python3 bench.py --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
+B="python3 bench.py --full --steps 40 --warmup 5 --rad-eq-max 1 --no-binning --no-cpu-baseline --no-c5 --no-per-species --no-chemistry"
 for r in 1 2 3; do
   for lib in default wt2; do
     if [ $lib = default ]; then unset FREI_HIP_LIB; else export FREI_HIP_LIB=abv/$lib.so; fi
