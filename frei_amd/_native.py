@@ -37,6 +37,12 @@ SIGNATURES = {
     "frei_set_ftoa_batch": (ctypes.c_int, [_vp, _dp]),
     "frei_run_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                       ctypes.c_double, _ip, _dp, _dp]),
+    "frei_run_batch_ex": (ctypes.c_int, [_vp, _dp, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                         ctypes.c_double, _ip, _dp, _dp, _dp, ctypes.c_int]),
+    "frei_get_dtaus_batch": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp]),
+    "frei_post_batch": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_double,
+                                       _dp, _dp, _dp]),
+    "frei_post_timing": (ctypes.c_int, [_vp, _dp]),
     "frei_set_grid": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_double,
                                      ctypes.c_double]),
     "frei_set_table": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp,

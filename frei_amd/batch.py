@@ -8,18 +8,19 @@ ratios.  Every sweep is one launch over (wavelength block, atmosphere); the per-
 species contraction is one dense product per layer on fp64 MFMA (K7).  Across GPUs the
 atmospheres are sharded with no exchange.
 """
+import collections
 import ctypes
 
 import numpy as np
 
 from . import _native as N
 from .chemistry import chemistry
-from .constants import BAR, K_B, M_BAR_DEFAULT, UM
+from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, SIGMA_SB, UM
 from .engine import EMIT, Engine, f_toa, planck_prefactor, trapz_weights
 from .opacity import sigma_scattering
 from .units import scalar, value
 
-__all__ = ["BatchEngine", "batched_emission_spectra"]
+__all__ = ["BatchEngine", "BatchRecord", "BatchResult", "batched_emission_spectra"]
 
 
 class BatchEngine:
@@ -84,18 +85,101 @@ class BatchEngine:
         except Exception:
             pass
 
-    def run(self, T_init, n_timesteps=1, n_zero_crossings=2, convergence_dT=3.0, alpha=1.0):
+    def run(self, T_init, n_timesteps=1, n_zero_crossings=2, convergence_dT=3.0, alpha=1.0,
+            want_hist=False, keep_dtaus=False):
         """Every atmosphere's emission_spectrum (core.py:233-338) -> dict(spectra [n_atm]
-        [n_lam], final_T [n_atm][n_layers], n_iter [n_atm])."""
+        [n_lam], final_T [n_atm][n_layers], n_iter [n_atm]).  ``want_hist`` adds ``temp_hist``:
+        a list of n_atm arrays, the m-th (n_layers, 2 * n_iter[m]) as Grid.emission_spectrum
+        returns it.  ``keep_dtaus`` leaves every atmosphere's final-emit dtaus on the device
+        for :meth:`get_dtaus` and :meth:`post` (n_atm * n_layers * n_lam doubles, allocated at
+        the first request)."""
         T = N.f64(np.broadcast_to(np.asarray(T_init, dtype=float), (self.n_atm, self.n_layers)))
         n_iter = (ctypes.c_int * self.n_atm)()
         T_final = np.empty((self.n_atm, self.n_layers))
         spectra = np.empty((self.n_atm, self.n_lam))
-        N.check(N.lib().frei_run_batch(self._ctx, N.dptr(T), int(n_timesteps),
-                                       int(n_zero_crossings), float(convergence_dT),
-                                       float(alpha), n_iter, N.dptr(T_final),
-                                       N.dptr(spectra)))
-        return dict(spectra=spectra, final_T=T_final, n_iter=np.array(list(n_iter)))
+        if not (want_hist or keep_dtaus):
+            N.check(N.lib().frei_run_batch(self._ctx, N.dptr(T), int(n_timesteps),
+                                           int(n_zero_crossings), float(convergence_dT),
+                                           float(alpha), n_iter, N.dptr(T_final),
+                                           N.dptr(spectra)))
+            return dict(spectra=spectra, final_T=T_final, n_iter=np.array(list(n_iter)))
+        hist = (np.empty((self.n_atm, self.n_layers, 2 * int(n_timesteps)))
+                if want_hist else None)
+        N.check(N.lib().frei_run_batch_ex(self._ctx, N.dptr(T), int(n_timesteps),
+                                          int(n_zero_crossings), float(convergence_dT),
+                                          float(alpha), n_iter, N.dptr(T_final),
+                                          N.dptr(spectra), N.dptr(hist), 1 if keep_dtaus else 0))
+        out = dict(spectra=spectra, final_T=T_final, n_iter=np.array(list(n_iter)))
+        if want_hist:
+            out["temp_hist"] = [hist[m][:, :2 * int(out["n_iter"][m])].copy()
+                                for m in range(self.n_atm)]
+        return out
+
+    def get_dtaus(self, m):
+        """Atmosphere ``m``'s dtaus (n_layers, n_lam) of the last ``run(keep_dtaus=True)``;
+        row 0 is the ones placeholder (Q12)."""
+        out = np.empty((self.n_layers, self.n_lam))
+        N.check(N.lib().frei_get_dtaus_batch(self._ctx, int(m), 1, N.dptr(out)))
+        return out
+
+    def get_temperatures(self):
+        T = np.empty((self.n_atm, self.n_layers))
+        N.check(N.lib().frei_get_temperatures(self._ctx, N.dptr(T)))
+        return T
+
+    def post(self, dtaus=None, spectra=None, T=None, want_p_milne=False, want_cf=False):
+        """effective_temperature (core.py:386-439) of every atmosphere, and on request the
+        per-wavelength Milne pressures and the contribution functions (plot.py:63-79), in one
+        device launch (frei_post_batch).  ``dtaus`` [n_atm][n_layers][n_lam], ``spectra``
+        [n_atm][n_lam] and ``T`` [n_atm][n_layers] are host arrays, or None for the state the
+        last ``run(keep_dtaus=True)`` left on the device.  Returns dict(T_milne, T_planck, T_eff
+        [n_atm] each; p_milne [n_atm][n_lam] and cf [n_atm][n_layers][n_lam], rows bottom-first,
+        when asked; sums [n_atm][3] = the device's (sum p_milne w, sum w, sum F trapz_w)).
+        The device returns the three wavelength sums per atmosphere; the scalar
+        finish is the host's, as in frei_amd.core for one atmosphere."""
+        A, nL, n = self.n_atm, self.n_layers, self.n_lam
+
+        def arr(x, shape, name):
+            if x is None:
+                return None
+            x = N.f64(x)
+            if x.shape != shape:
+                raise ValueError(f"{name} must have shape {shape}, not {x.shape}")
+            return x
+        d = arr(dtaus, (A, nL, n), "dtaus")
+        sp = arr(spectra, (A, n), "spectra")
+        Th = arr(T, (A, nL), "T")
+        p = np.asarray(self.p_bar, dtype=float)
+        lam_cm = N.f64(self.lam_um * UM)
+        nu = ratio = cf = None
+        if want_cf:     # formed as Engine.contribution forms them
+            dlogP = (np.log10(p.max()) - np.log10(p.min())) / (len(p) - 1)
+            k = 10 ** -dlogP
+            ratio = N.f64(p / ((1 - k) * p))
+            nu = N.f64(1.0 / (self.lam_um * UM))
+            cf = np.empty((A, nL, n))
+        pm = np.empty((A, n)) if want_p_milne else None
+        sums = np.empty((A, 3))
+        N.check(N.lib().frei_post_batch(self._ctx, N.dptr(d), N.dptr(sp), N.dptr(Th),
+                                        N.dptr(N.f64(p)), N.dptr(lam_cm), N.dptr(nu),
+                                        N.dptr(ratio), H * C / K_B, N.dptr(sums), N.dptr(pm),
+                                        N.dptr(cf)))
+        if Th is None:
+            Th = self.get_temperatures()
+        T_milne = np.array([np.interp(sums[m, 0] / sums[m, 1], p[::-1], Th[m][::-1])
+                            for m in range(A)])
+        T_planck = (sums[:, 2] / SIGMA_SB) ** 0.25
+        T_eff = np.array([float(np.mean([T_milne[m], T_planck[m]])) for m in range(A)])
+        out = dict(T_milne=T_milne, T_planck=T_planck, T_eff=T_eff, sums=sums)
+        if want_p_milne:
+            out["p_milne"] = pm
+        if want_cf:
+            out["cf"] = cf
+        return out
+
+    def post_timing(self):
+        """HIP-event milliseconds of the last :meth:`post` call's kernels."""
+        return Engine.post_timing(self)
 
     # fixed-work driver pieces (benchmarks)
     def state_init(self, T_init):
@@ -135,11 +219,51 @@ class BatchEngine:
     path = Engine.path
 
 
+BatchRecord = collections.namedtuple(
+    "BatchRecord", "spectrum final_T n_iter temp_hist T_eff T_milne T_planck")
+BatchRecord.__doc__ = """One atmosphere of ``batched_emission_spectra(..., post=True)``: what
+Grid.emission_spectrum returns (spectrum, final_T, temp_hist; core.py:335-338) with its iteration
+count, and effective_temperature's three values (core.py:386-439), K."""
+
+
+class BatchResult(list):
+    """The :class:`BatchRecord` list of ``batched_emission_spectra(..., post=True)``.  It keeps
+    the batched engine (``engine``, with every atmosphere's dtaus on the device) until
+    :meth:`close`, so per-atmosphere arrays are fetched only when asked for."""
+
+    def __init__(self, records, engine):
+        super().__init__(records)
+        self.engine = engine
+        self._cf = None
+
+    def dtaus(self, m):
+        """Atmosphere ``m``'s dtaus (n_layers, n_lam), as Grid.emission_spectrum returns them."""
+        return self.engine.get_dtaus(m)
+
+    def contribution(self, m):
+        """Atmosphere ``m``'s contribution function (plot.py:63-79), rows bottom-first.  The
+        first call computes every atmosphere's in one launch and keeps them on the host."""
+        if self._cf is None:
+            self._cf = self.engine.post(want_cf=True)["cf"]
+        return self._cf[m]
+
+    def close(self):
+        self.engine.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def batched_emission_spectra(grids, n_timesteps=1, n_zero_crossings=2, convergence_dT=3.0,
-                             device=0):
+                             device=0, post=False):
     """Grid.emission_spectrum for a list of Grids that share wavelengths, pressures and
     opacity tables (a grid sweep over T, g and metallicity), as one batched device run.
-    Returns [(Spectrum, final_T, n_iter)] in the order of ``grids``."""
+    Returns [(Spectrum, final_T, n_iter)] in the order of ``grids``; with ``post=True`` a
+    :class:`BatchResult` of :class:`BatchRecord` (spectrum, final_T, n_iter, temp_hist, T_eff,
+    T_milne, T_planck) that keeps the engine for ``contribution(m)`` and ``dtaus(m)``."""
     from .core import F_TOA, Spectrum
     g0 = grids[0]
     for gr in grids[1:]:
@@ -167,9 +291,23 @@ def batched_emission_spectra(grids, n_timesteps=1, n_zero_crossings=2, convergen
         ft = ft[0]
     eng = BatchEngine(g0.lam, g0.pressures, g0.opacities, [gr.planet.g for gr in grids],
                       mmr=np.array(mmrs), m_bar=pl.m_bar, F_toa=ft, device=device)
+    T_init = np.array([gr.init_temperatures for gr in grids])
+    if post:
+        try:
+            out = eng.run(T_init, n_timesteps, n_zero_crossings, scalar(convergence_dT, "K"),
+                          pl.alpha, want_hist=True, keep_dtaus=True)
+            te = eng.post()
+        except BaseException:
+            eng.close()
+            raise
+        return BatchResult(
+            [BatchRecord(Spectrum(out["spectra"][m], g0.lam), out["final_T"][m],
+                         int(out["n_iter"][m]), out["temp_hist"][m], float(te["T_eff"][m]),
+                         float(te["T_milne"][m]), float(te["T_planck"][m]))
+             for m in range(len(grids))], eng)
     try:
-        out = eng.run(np.array([gr.init_temperatures for gr in grids]), n_timesteps,
-                      n_zero_crossings, scalar(convergence_dT, "K"), pl.alpha)
+        out = eng.run(T_init, n_timesteps, n_zero_crossings, scalar(convergence_dT, "K"),
+                      pl.alpha)
     finally:
         eng.close()
     return [(Spectrum(out["spectra"][m], g0.lam), out["final_T"][m], int(out["n_iter"][m]))

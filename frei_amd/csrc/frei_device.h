@@ -475,6 +475,18 @@ void launch_milne(const double* dtaus, int nL, int64_t n, const double* fp, doub
 void launch_contribution(const double* dtaus, int nL, int64_t n, const double* nu,
                          const double* ratio, const double* T, double hcperk, double* cf,
                          hipStream_t st);
+// x[r * stride + i] = v for i < n, r < rows.
+void launch_fill_rows(double* x, int64_t n, int64_t stride, int rows, double v, hipStream_t st);
+// Batched post-processing over (wavelength block, atmosphere): Milne pressures (p_milne may be
+// null), the contribution function when cf is non-null, and sums[n_atm][3] = (sum p_milne w,
+// sum w, sum F trapz_w) with w = F_top * lam_cm, reduced in a fixed order through
+// part[n_atm][3][post_batch_blocks(n)].  Atmosphere m's emergent row is F_top + m * f_stride.
+int post_batch_blocks(int64_t n);
+void launch_post_batch(const double* dtaus, const double* F_top, int64_t f_stride,
+                       const double* T, const double* fp, const double* lam_cm,
+                       const double* wtr, const double* nu, const double* ratio, double hcperk,
+                       int nL, int64_t n, int n_atm, double* p_milne, double* cf, double* part,
+                       double* sums, hipStream_t st);
 void launch_contract_batch(const double* const* tabs, int S, const double* mmr,
                            const int32_t* prow, int n_layers, int n_T, int64_t pitch,
                            int n_atm, int64_t tab_stride, double* eff, hipStream_t st);

@@ -3296,12 +3296,11 @@ __device__ int np_search(double key, int len, int guess, const Arr& arr) {
 
 // effective_temperature_milne, per wavelength (core.py:392-395):
 // p_milne[j] = np.interp(2/3, exp(-dtaus[:, j]), p_bar) with numpy's search and formula.
-__global__ __launch_bounds__(256) void milne_kernel(const double* __restrict__ dtaus, int nL,
-                                                    int64_t n, const double* __restrict__ fp,
-                                                    double* __restrict__ out) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  auto X = [&](int l) { return exp(-dtaus[(int64_t)l * n + j]); };
+// One column: dtaus points at the column's row 0, rows are n apart.  Shared by the single and
+// the batched kernel (the same operations in the same order: bitwise the same result).
+__device__ __forceinline__ double milne_column(const double* __restrict__ dtaus, int nL,
+                                               int64_t n, const double* __restrict__ fp) {
+  auto X = [&](int l) { return exp(-dtaus[(int64_t)l * n]); };
   const double key = 2.0 / 3.0;
   const int k = np_search(key, nL, 0, X);
   double r;
@@ -3323,32 +3322,175 @@ __global__ __launch_bounds__(256) void milne_kernel(const double* __restrict__ d
       }
     }
   }
-  out[j] = r;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void milne_kernel(const double* __restrict__ dtaus, int nL,
+                                                    int64_t n, const double* __restrict__ fp,
+                                                    double* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  out[j] = milne_column(dtaus + j, nL, n, fp);
 }
 
 // Contribution function (plot.py:63-79) per wavelength, layers top-first (the reference's
 // reversed arrays): tau = cumsum of dtau; cf = ((exp(-tau) * dtau) * ratio) * nu^3 /
 // expm1((hc/k * nu) / T), ratio = p / dP; then cf /= sum over layers (sequential, top
-// first).  Written bottom-first (cf[::-1], as plotted).
+// first).  Written bottom-first (cf[::-1], as plotted).  One column: dtaus and cf point at the
+// column's row 0, rows are n apart; v = nu of the column.  Shared by the single and the batched
+// kernel.
+__device__ __forceinline__ void contribution_column(const double* __restrict__ dtaus, int nL,
+                                                    int64_t n, double v,
+                                                    const double* __restrict__ ratio,
+                                                    const double* __restrict__ T, double hcperk,
+                                                    double* __restrict__ cf) {
+  const double v3 = pow(v, 3.0);
+  const double hv = hcperk * v;
+  double tau = 0.0, sum = 0.0;
+  for (int m = 0; m < nL; ++m) {
+    const int l = nL - 1 - m;
+    const double d = dtaus[(int64_t)l * n];
+    tau = (m == 0) ? d : tau + d;
+    const double c = (((exp(-tau) * d) * ratio[l]) * v3) / expm1(hv / T[l]);
+    cf[(int64_t)l * n] = c;
+    sum = (m == 0) ? c : sum + c;
+  }
+  for (int l = 0; l < nL; ++l) cf[(int64_t)l * n] = cf[(int64_t)l * n] / sum;
+}
+
 __global__ __launch_bounds__(256) void contribution_kernel(
     const double* __restrict__ dtaus, int nL, int64_t n, const double* __restrict__ nu,
     const double* __restrict__ ratio, const double* __restrict__ T, double hcperk,
     double* __restrict__ cf) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  const double v = nu[j];
-  const double v3 = pow(v, 3.0);
-  const double hv = hcperk * v;
-  double tau = 0.0, sum = 0.0;
-  for (int m = 0; m < nL; ++m) {
-    const int l = nL - 1 - m;
-    const double d = dtaus[(int64_t)l * n + j];
-    tau = (m == 0) ? d : tau + d;
-    const double c = (((exp(-tau) * d) * ratio[l]) * v3) / expm1(hv / T[l]);
-    cf[(int64_t)l * n + j] = c;
-    sum = (m == 0) ? c : sum + c;
+  contribution_column(dtaus + j, nL, n, nu[j], ratio, T, hcperk, cf + j);
+}
+
+// Batched post-processing (§8(f) #3 for a batched context): one launch over (256-wavelength
+// block, atmosphere), one lane per wavelength.  Per (atmosphere m, wavelength j): the Milne
+// pressure of column j of dtaus[m] (milne_column) and, with CF, the column of the contribution
+// function with atmosphere m's temperatures (contribution_column).  Fused into the same pass,
+// the three sums effective_temperature needs (core.py:397-414), all of non-negative terms:
+//   A = sum_j p_milne[j] * w[j],  B = sum_j w[j],  w[j] = F_top[j] * lam_cm[j] (rounded once),
+//   C = sum_j F_top[j] * trapz_w[j]            (np.trapz(F, lam) as per-point weights).
+// Fixed order, no atomics: the wave's DPP tree (wave_sum4; lanes past n add +0.0), the block's
+// four waves in wave order, one partial per (atmosphere, quantity, block) in part[m][q][block];
+// post_batch_reduce_kernel sums the blocks.  Bitwise the same from run to run.
+struct PostBatchArgs {
+  const double* dtaus;    // [n_atm][nL][n]
+  const double* F_top;    // atmosphere m's emergent row at F_top + m * f_stride
+  int64_t f_stride;
+  const double* T;        // [n_atm][nL]
+  const double* fp;       // p_bar[nL]
+  const double* lam_cm;   // [n]
+  const double* wtr;      // [n] trapezoid weights
+  const double* nu;       // [n]      (CF)
+  const double* ratio;    // [nL]     (CF)
+  double hcperk;
+  double* p_milne;        // [n_atm][n] or null
+  double* cf;             // [n_atm][nL][n] (CF)
+  double* part;           // [n_atm][3][gridDim.x]
+  int nL;
+  int64_t n;
+};
+
+template <bool CF>
+__global__ __launch_bounds__(256) void post_batch_kernel(PostBatchArgs a) {
+  __shared__ double sh[3][4];
+  const int m = blockIdx.y;
+  const int64_t n = a.n;
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  double qa = 0.0, qb = 0.0, qc = 0.0;
+  if (j < n) {
+    const double* dt = a.dtaus + (int64_t)m * a.nL * n + j;
+    const double pm = milne_column(dt, a.nL, n, a.fp);
+    if (a.p_milne) a.p_milne[(int64_t)m * n + j] = pm;
+    const double F = a.F_top[(int64_t)m * a.f_stride + j];
+    const double w = F * a.lam_cm[j];
+    qa = pm * w;
+    qb = w;
+    qc = F * a.wtr[j];
+    if constexpr (CF)
+      contribution_column(dt, a.nL, n, a.nu[j], a.ratio, a.T + (int64_t)m * a.nL, a.hcperk,
+                          a.cf + (int64_t)m * a.nL * n + j);
   }
-  for (int l = 0; l < nL; ++l) cf[(int64_t)l * n + j] = cf[(int64_t)l * n + j] / sum;
+  // whole wave again: lane 0 ends with sum(qa), lane 2 with sum(qb), lane 1 with sum(qc)
+  const double s = wave_sum4(qa, qb, qc, 0.0, lane);
+  if (lane < 3) sh[lane == 0 ? 0 : (lane == 2 ? 1 : 2)][wave] = s;
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int q = threadIdx.x;
+    double v = sh[q][0];
+    for (int w = 1; w < 4; ++w) v += sh[q][w];
+    a.part[((int64_t)m * 3 + q) * gridDim.x + blockIdx.x] = v;
+  }
+}
+
+// The block partials of post_batch_kernel in block order: one workgroup per (quantity,
+// atmosphere); each thread adds every kRedThreads-th block, then reduce_kernel's fixed tree
+// (wave butterfly, waves in order).
+__global__ __launch_bounds__(kRedThreads) void post_batch_reduce_kernel(
+    const double* __restrict__ part, int nblocks, double* __restrict__ sums) {
+  __shared__ double sh[kRedWaves];
+  const int64_t row = (int64_t)blockIdx.y * 3 + blockIdx.x;
+  part += row * nblocks;
+  double acc = 0.0;
+  for (int b = threadIdx.x; b < nblocks; b += kRedThreads) acc += part[b];
+  acc = butterfly_sum(acc, threadIdx.x & 63);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double v = sh[0];
+    for (int w = 1; w < kRedWaves; ++w) v += sh[w];
+    sums[row] = v;
+  }
+}
+
+// x[r * stride + i] = v for i < n, r < rows (row 0 of every atmosphere's dtaus, Q12).
+__global__ void fill_rows_kernel(double* x, int64_t n, int64_t stride, double v) {
+  x += (int64_t)blockIdx.y * stride;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < n;
+       idx += (int64_t)gridDim.x * blockDim.x)
+    x[idx] = v;
+}
+
+void launch_fill_rows(double* x, int64_t n, int64_t stride, int rows, double v, hipStream_t st) {
+  const int nb = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(fill_rows_kernel, dim3(nb > 0 ? nb : 1, (unsigned)rows), dim3(256), 0, st,
+                     x, n, stride, v);
+}
+
+int post_batch_blocks(int64_t n) { return (int)((n + 255) / 256); }
+
+void launch_post_batch(const double* dtaus, const double* F_top, int64_t f_stride,
+                       const double* T, const double* fp, const double* lam_cm,
+                       const double* wtr, const double* nu, const double* ratio, double hcperk,
+                       int nL, int64_t n, int n_atm, double* p_milne, double* cf, double* part,
+                       double* sums, hipStream_t st) {
+  PostBatchArgs a{};
+  a.dtaus = dtaus;
+  a.F_top = F_top;
+  a.f_stride = f_stride;
+  a.T = T;
+  a.fp = fp;
+  a.lam_cm = lam_cm;
+  a.wtr = wtr;
+  a.nu = nu;
+  a.ratio = ratio;
+  a.hcperk = hcperk;
+  a.p_milne = p_milne;
+  a.cf = cf;
+  a.part = part;
+  a.nL = nL;
+  a.n = n;
+  const int nb = post_batch_blocks(n);
+  const dim3 grid((unsigned)nb, (unsigned)n_atm);
+  if (cf) hipLaunchKernelGGL(post_batch_kernel<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(post_batch_kernel<false>, grid, dim3(256), 0, st, a);
+  hipLaunchKernelGGL(post_batch_reduce_kernel, dim3(3, (unsigned)n_atm), dim3(kRedThreads), 0,
+                     st, part, nb, sums);
 }
 
 void launch_milne(const double* dtaus, int nL, int64_t n, const double* fp, double* out,

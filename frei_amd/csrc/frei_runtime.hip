@@ -194,6 +194,11 @@ struct frei_ctx {
   double* d_g = nullptr;      // [n_atm] gravity (batched)
   size_t eff_stride = 0;      // elements per atmosphere of d_eff
   int* h_conv = nullptr;      // pinned [2][n_atm] convergence flags (frei_run_batch)
+  bool batch_api = false;     // created through frei_ctx_create_batch (n_atm may be 1)
+  // d_dtaus holds every atmosphere's final-emit dtaus [n_atm][nL][nlam] of the last
+  // frei_run_batch_ex(keep_dtaus) and d_T / d_Fu are still that run's (frei_post_batch)
+  bool dtaus_batch_valid = false;
+  double post_ms = 0.0;       // HIP-event time of the last post-processing call's kernels
   double *d_part = nullptr, *d_Fb = nullptr, *d_Fb_all = nullptr;
   // T-P loop state
   int* d_conv = nullptr;
@@ -1230,6 +1235,26 @@ int ensure_dtaus(frei_ctx* c) {
   return 0;
 }
 
+// Every atmosphere's dtaus [n_atm][nL][nlam] of a batched context, allocated on the first
+// request only (n_atm = 1: ensure_dtaus' buffer); row 0 of every atmosphere is the ones
+// placeholder (Q12).  A failed allocation names its size and leaves the context as it was.
+int ensure_dtaus_batch(frei_ctx* c) {
+  if (c->n_atm == 1) return ensure_dtaus(c);
+  const size_t per = (size_t)c->nL * c->nlam, n = per * c->n_atm;
+  if (!c->d_dtaus) {
+    double* p = nullptr;
+    if (hipMalloc((void**)&p, n * sizeof(double)) != hipSuccess) {
+      (void)hipGetLastError();   // not sticky: later launch checks must not see it
+      return fail("cannot allocate " + std::to_string(n * sizeof(double)) + " bytes for " +
+                  std::to_string(c->n_atm) + " atmospheres' dtaus (keep_dtaus)");
+    }
+    c->d_dtaus = p;
+  }
+  launch_fill_rows(c->d_dtaus, c->nlam, (int64_t)per, c->n_atm, 1.0, c->stream);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 bool ready(frei_ctx* c) { return c && c->grid_set; }
 
 // Tuning knobs (frei_set_option and FREI_<NAME> environment variables); each takes effect at
@@ -1416,7 +1441,9 @@ int frei_ctx_create(frei_ctx** out, int device, int n_layers, int64_t n_lam, int
 
 int frei_ctx_create_batch(frei_ctx** out, int device, int n_layers, int64_t n_lam,
                           int n_species, int n_atm) {
-  return ctx_create(out, device, n_layers, n_lam, n_species, n_atm);
+  TRY(ctx_create(out, device, n_layers, n_lam, n_species, n_atm));
+  (*out)->batch_api = true;
+  return 0;
 }
 
 int frei_ctx_destroy(frei_ctx* c) {
@@ -1801,6 +1828,7 @@ int frei_sweep(frei_ctx* c, int direction, double alpha, double* dT, double* bol
     o.dtaus = c->d_dtaus;
   }
   c->dtaus_valid = false;
+  c->dtaus_batch_valid = false;
   launch_setup(setup_args(c), direction, c->stream);
   HIP_TRY(hipGetLastError());
   TRY(run_sweep(c, o));
@@ -1827,6 +1855,7 @@ int frei_sweep(frei_ctx* c, int direction, double alpha, double* dT, double* bol
 int frei_state_init(frei_ctx* c, const double* T_init) {
   if (!ready(c) || !T_init) return fail("context not ready or null T_init");
   TRY(set_device(c));
+  c->dtaus_batch_valid = false;   // the kept dtaus belong to the state this call replaces
   TRY(build_meta(c));
   c->has_pend = false;   // an update deferred by an interrupted run must not land on the new T
   home_temperatures(c);
@@ -1928,6 +1957,7 @@ int frei_iterate(frei_ctx* c, int n, int n_zero_crossings, double convergence_dT
                  double alpha) {
   if (!ready(c)) return fail("context not ready");
   TRY(set_device(c));
+  c->dtaus_batch_valid = false;
   TRY(ensure_hist(c, 1));
   const bool stop = n_zero_crossings >= 0;
   return iterate(c, n, stop ? n_zero_crossings : 0x7fffffff, convergence_dT, alpha, stop);
@@ -2030,10 +2060,22 @@ int frei_run(frei_ctx* c, const double* T_init, int n_timesteps, int n_zero_cros
 int frei_run_batch(frei_ctx* c, const double* T_init, int n_timesteps, int n_zero_crossings,
                    double convergence_dT, double alpha, int* n_iter, double* T_final,
                    double* spectra) {
+  return frei_run_batch_ex(c, T_init, n_timesteps, n_zero_crossings, convergence_dT, alpha,
+                           n_iter, T_final, spectra, nullptr, 0);
+}
+
+int frei_run_batch_ex(frei_ctx* c, const double* T_init, int n_timesteps, int n_zero_crossings,
+                      double convergence_dT, double alpha, int* n_iter, double* T_final,
+                      double* spectra, double* temp_hist, int keep_dtaus) {
   if (!ready(c) || !T_init || !n_iter) return fail("context not ready or null argument");
   if (n_timesteps < 1) return fail("n_timesteps must be >= 1");
   TRY(set_device(c));
   TRY(ensure_hist(c, n_timesteps));
+  c->dtaus_batch_valid = false;
+  if (keep_dtaus) {   // before the state changes: a failed allocation leaves the context as it was
+    TRY(ensure_dtaus_batch(c));
+    c->dtaus_valid = false;   // the buffer no longer holds a frei_run's dtaus
+  }
   TRY(frei_state_init(c, T_init));
   const int A = c->n_atm;
   int* flags = c->h_conv ? c->h_conv : c->h_flag;   // pinned [2][A]
@@ -2061,10 +2103,27 @@ int frei_run_batch(frei_ctx* c, const double* T_init, int n_timesteps, int n_zer
   f.dir = kEmit;
   f.force = 1;
   f.alpha = 1.0;
+  if (keep_dtaus) f.dtaus = c->d_dtaus;   // every sweep form offsets it by the atmosphere
   TRY(run_sweep(c, f));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  c->dtaus_batch_valid = keep_dtaus != 0;
   HIP_TRY(hipMemcpy(n_iter, c->d_iter, A * sizeof(int), hipMemcpyDeviceToHost));
   const size_t nL = c->nL;
+  if (temp_hist) {   // [n_atm][n_layers][2 * n_timesteps], zero past 2 * n_iter[m] columns
+    const size_t cols = 2 * (size_t)n_timesteps;
+    std::fill(temp_hist, temp_hist + (size_t)A * nL * cols, 0.0);
+    std::vector<double> h;
+    for (int m = 0; m < A; ++m) {
+      const size_t it = (size_t)std::min(std::max(n_iter[m], 0), n_timesteps);
+      if (it == 0) continue;
+      h.resize(it * 2 * nL);
+      HIP_TRY(hipMemcpy(h.data(), c->d_hist + (size_t)m * c->hist_cap * 2 * nL,
+                        h.size() * sizeof(double), hipMemcpyDeviceToHost));
+      double* out = temp_hist + (size_t)m * nL * cols;
+      for (size_t l = 0; l < nL; ++l)
+        for (size_t col = 0; col < 2 * it; ++col) out[l * cols + col] = h[col * nL + l];
+    }
+  }
   if (T_final)
     HIP_TRY(hipMemcpy(T_final, c->d_T, nL * A * sizeof(double), hipMemcpyDeviceToHost));
   if (spectra)  // F_up[n_layers - 1] of every atmosphere
@@ -2316,24 +2375,52 @@ static int post_dtaus(frei_ctx* c, const double* h, double** tmp, const double**
   return 0;
 }
 
+// HIP events around a post-processing call's kernels (frei_post_timing): begin() before the
+// launches, end() after them, read() once the stream is synchronised.
+struct PostTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  void begin(hipStream_t st) {
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
+        hipEventRecord(e0, st) != hipSuccess)
+      drop();
+  }
+  void end(hipStream_t st) {
+    if (e0 && hipEventRecord(e1, st) != hipSuccess) drop();
+  }
+  void read(frei_ctx* c) {
+    float ms = 0.f;
+    c->post_ms = (e0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ? (double)ms : 0.0;
+    drop();
+  }
+  void drop() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    e0 = e1 = nullptr;
+  }
+};
+
 int frei_milne_pressure(frei_ctx* c, const double* dtaus, const double* p_bar,
                         double* p_milne) {
   if (!ready(c) || !p_bar || !p_milne) return fail("context not ready or null argument");
   TRY(set_device(c));
   double *tmp = nullptr, *d_fp = nullptr, *d_out = nullptr;
   const double* d_dt = nullptr;
+  PostTimer tm;
   int rc = post_dtaus(c, dtaus, &tmp, &d_dt);
   if (!rc) rc = dalloc(&d_fp, c->nL);
   if (!rc) rc = dalloc(&d_out, c->nlam);
   if (!rc) rc = h2d(d_fp, p_bar, c->nL, c->stream);
   if (!rc) {
+    tm.begin(c->stream);
     launch_milne(d_dt, c->nL, c->nlam, d_fp, d_out, c->stream);
     if (hipGetLastError() != hipSuccess) rc = fail("milne kernel launch failed");
+    tm.end(c->stream);
   }
   if (!rc && hipMemcpyAsync(p_milne, d_out, c->nlam * sizeof(double), hipMemcpyDeviceToHost,
                             c->stream) != hipSuccess)
     rc = fail("milne copy failed");
   if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("milne kernel failed");
+  tm.read(c);
   dfree(tmp), dfree(d_fp), dfree(d_out);
   return rc;
 }
@@ -2353,16 +2440,106 @@ int frei_contribution(frei_ctx* c, const double* dtaus, const double* nu, const 
   if (!rc) rc = h2d(d_nu, nu, c->nlam, c->stream);
   if (!rc) rc = h2d(d_ratio, ratio, c->nL, c->stream);
   if (!rc) rc = h2d(d_T, T, c->nL, c->stream);
+  PostTimer tm;
   if (!rc) {
+    tm.begin(c->stream);
     launch_contribution(d_dt, c->nL, c->nlam, d_nu, d_ratio, d_T, hcperk, d_cf, c->stream);
     if (hipGetLastError() != hipSuccess) rc = fail("contribution kernel launch failed");
+    tm.end(c->stream);
   }
   if (!rc && hipMemcpyAsync(cf, d_cf, n * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
                  hipSuccess)
     rc = fail("contribution copy failed");
   if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("contribution kernel failed");
+  tm.read(c);
   dfree(tmp), dfree(d_nu), dfree(d_ratio), dfree(d_T), dfree(d_cf);
   return rc;
+}
+
+int frei_get_dtaus_batch(frei_ctx* c, int atm_lo, int n, double* out) {
+  if (!ready(c) || !out) return fail("context not ready or null argument");
+  if (!c->batch_api) return fail("not a batched context: frei_run returns a single context's dtaus");
+  if (atm_lo < 0 || n < 0 || (int64_t)atm_lo + n > c->n_atm)
+    return fail("atmosphere range outside [0, n_atm)");
+  if (!c->dtaus_batch_valid || !c->d_dtaus)
+    return fail("no device dtaus: run frei_run_batch_ex with keep_dtaus first");
+  TRY(set_device(c));
+  const size_t per = (size_t)c->nL * c->nlam;
+  if (n > 0)
+    HIP_TRY(hipMemcpy(out, c->d_dtaus + (size_t)atm_lo * per, (size_t)n * per * sizeof(double),
+                      hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int frei_post_batch(frei_ctx* c, const double* dtaus, const double* spectra, const double* T,
+                    const double* p_bar, const double* lam_cm, const double* nu,
+                    const double* ratio, double hcperk, double* sums, double* p_milne,
+                    double* cf) {
+  if (!ready(c) || !p_bar || !lam_cm || !sums) return fail("context not ready or null argument");
+  if (cf && (!nu || !ratio)) return fail("null nu or ratio with cf requested");
+  if (!c->batch_api)
+    return fail("frei_post_batch needs a context from frei_ctx_create_batch: on a single "
+                "context use frei_milne_pressure / frei_contribution");
+  if ((!dtaus || !spectra || (cf && !T)) && (!c->dtaus_batch_valid || !c->d_dtaus))
+    return fail("no device dtaus: run frei_run_batch_ex with keep_dtaus first, or pass dtaus, "
+                "spectra and T");
+  TRY(set_device(c));
+  const size_t A = c->n_atm, nL = c->nL, n = c->nlam, per = nL * n;
+  const int nb = post_batch_blocks(c->nlam);
+  double *u_dt = nullptr, *u_sp = nullptr, *u_T = nullptr, *d_fp = nullptr, *d_lam = nullptr,
+         *d_nu = nullptr, *d_ratio = nullptr, *d_pm = nullptr, *d_cf = nullptr,
+         *d_part = nullptr, *d_sums = nullptr;
+  PostTimer tm;
+  int rc = 0;
+  if (dtaus && !(rc = dalloc(&u_dt, A * per))) rc = h2d(u_dt, dtaus, A * per, c->stream);
+  if (!rc && spectra && !(rc = dalloc(&u_sp, A * n))) rc = h2d(u_sp, spectra, A * n, c->stream);
+  if (!rc && cf && T && !(rc = dalloc(&u_T, A * nL))) rc = h2d(u_T, T, A * nL, c->stream);
+  if (!rc) rc = dalloc(&d_fp, nL);
+  if (!rc) rc = dalloc(&d_lam, n);
+  if (!rc) rc = dalloc(&d_part, A * 3 * (size_t)nb);
+  if (!rc) rc = dalloc(&d_sums, A * 3);
+  if (!rc && p_milne) rc = dalloc(&d_pm, A * n);
+  if (!rc && cf) {
+    rc = dalloc(&d_nu, n);
+    if (!rc) rc = dalloc(&d_ratio, nL);
+    if (!rc) rc = dalloc(&d_cf, A * per);
+    if (!rc) rc = h2d(d_nu, nu, n, c->stream);
+    if (!rc) rc = h2d(d_ratio, ratio, nL, c->stream);
+  }
+  if (!rc) rc = h2d(d_fp, p_bar, nL, c->stream);
+  if (!rc) rc = h2d(d_lam, lam_cm, n, c->stream);
+  if (!rc) {
+    // the emergent row F_up[n_layers - 1] of every atmosphere, in place in the flux state
+    const double* F_top = u_sp ? u_sp : c->d_Fu + (nL - 1) * n;
+    const int64_t f_stride = u_sp ? (int64_t)n : (int64_t)per;
+    tm.begin(c->stream);
+    launch_post_batch(u_dt ? u_dt : c->d_dtaus, F_top, f_stride, u_T ? u_T : c->d_T, d_fp, d_lam,
+                      c->d_wtr, d_nu, d_ratio, hcperk, c->nL, c->nlam, c->n_atm, d_pm, d_cf,
+                      d_part, d_sums, c->stream);
+    if (hipGetLastError() != hipSuccess) rc = fail("post-processing kernel launch failed");
+    tm.end(c->stream);
+  }
+  auto d2h = [&](double* h, const double* d, size_t cnt) {
+    if (!rc && hipMemcpyAsync(h, d, cnt * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
+                   hipSuccess)
+      rc = fail("post-processing copy failed");
+  };
+  d2h(sums, d_sums, A * 3);
+  if (p_milne) d2h(p_milne, d_pm, A * n);
+  if (cf) d2h(cf, d_cf, A * per);
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc)
+    rc = fail("post-processing kernel failed");
+  tm.read(c);
+  dfree(u_dt), dfree(u_sp), dfree(u_T), dfree(d_fp), dfree(d_lam), dfree(d_nu), dfree(d_ratio),
+      dfree(d_pm), dfree(d_cf), dfree(d_part), dfree(d_sums);
+  if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
+  return rc;
+}
+
+int frei_post_timing(frei_ctx* c, double* ms) {
+  if (!c || !ms) return fail("null argument");
+  *ms = c->post_ms;
+  return 0;
 }
 
 int frei_ctx_path(frei_ctx* c, int* flags) {

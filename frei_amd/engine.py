@@ -453,6 +453,13 @@ class Engine:
         N.check(N.lib().frei_contract_timing(self._ctx, ctypes.byref(ms), ctypes.byref(nb)))
         return dict(ms=ms.value, bytes=nb.value)
 
+    def post_timing(self):
+        """HIP-event milliseconds of the kernels of the last post-processing call
+        (milne_pressure, contribution, BatchEngine.post) on this context (frei_post_timing)."""
+        ms = ctypes.c_double(0)
+        N.check(N.lib().frei_post_timing(self._ctx, ctypes.byref(ms)))
+        return ms.value
+
     def kappa(self, T, p_bar):
         k = np.empty(self.n_lam)
         sig = np.empty(self.n_lam)

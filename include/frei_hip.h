@@ -58,8 +58,10 @@ int frei_ctx_create(frei_ctx** out, int device, int n_layers, int64_t n_lam, int
  * Grid.emission_spectrum (core.py:233-338) run independently.  Needs tables on shared
  * on-node p/T nodes without NaN; the per-atmosphere species contraction runs on fp64 MFMA
  * (K7).  State accessors (set/get fluxes and temperatures) take n_atm blocks; frei_sweep,
- * frei_run, frei_kappa, post-processing and the rank exchange are single-atmosphere only
- * (batched runs shard atmospheres across ranks with no exchange).
+ * frei_run, frei_kappa and the rank exchange are single-atmosphere only (batched runs shard
+ * atmospheres across ranks with no exchange).  Post-processing of every atmosphere of a
+ * batched run is frei_run_batch_ex(keep_dtaus) + frei_post_batch below; frei_milne_pressure
+ * and frei_contribution stay the single-context calls.
  */
 int frei_ctx_create_batch(frei_ctx** out, int device, int n_layers, int64_t n_lam,
                           int n_species, int n_atm);
@@ -72,6 +74,24 @@ int frei_set_ftoa_batch(frei_ctx* ctx, const double* f_toa);
 int frei_run_batch(frei_ctx* ctx, const double* T_init, int n_timesteps, int n_zero_crossings,
                    double convergence_dT, double alpha, int* n_iter, double* T_final,
                    double* spectra);
+/*
+ * frei_run_batch with the rest of what the reference's Grid.emission_spectrum returns per
+ * atmosphere (core.py:335-338: spectrum, final temperatures, temperature history, dtaus);
+ * frei_run_batch is this call with temp_hist = NULL, keep_dtaus = 0.
+ *   temp_hist[n_atm][n_layers][2*n_timesteps] (may be NULL): atmosphere m's first
+ *     2*n_iter[m] columns are its absorb history (core.py:303-307, 320-321; transposed as in
+ *     frei_run), the rest are zero.
+ *   keep_dtaus != 0: the final emit (core.py:323-333) writes every atmosphere's dtaus into a
+ *     device buffer [n_atm][n_layers][n_lam], row 0 of every atmosphere = 1 (Q12), allocated
+ *     at the first request only; if that allocation fails the call returns an error naming
+ *     the size and the context stays usable.  The kept dtaus feed frei_get_dtaus_batch and
+ *     frei_post_batch until the next frei_state_init, frei_iterate or run without keep_dtaus.
+ */
+int frei_run_batch_ex(frei_ctx* ctx, const double* T_init, int n_timesteps,
+                      int n_zero_crossings, double convergence_dT, double alpha, int* n_iter,
+                      double* T_final, double* spectra, double* temp_hist, int keep_dtaus);
+/* The kept dtaus of atmospheres [atm_lo, atm_lo + n): out[n][n_layers][n_lam]. */
+int frei_get_dtaus_batch(frei_ctx* ctx, int atm_lo, int n, double* out);
 int frei_ctx_destroy(frei_ctx* ctx);
 
 /*
@@ -214,6 +234,36 @@ int frei_milne_pressure(frei_ctx* ctx, const double* dtaus, const double* p_bar,
                         double* p_milne);
 int frei_contribution(frei_ctx* ctx, const double* dtaus, const double* nu,
                       const double* ratio, const double* T, double hcperk, double* cf);
+/*
+ * The same post-processing for every atmosphere of a batched context (n_atm >= 1, from
+ * frei_ctx_create_batch) in one launch over (wavelength block, atmosphere); the reference
+ * calls effective_temperature (core.py:386-439) and the dashboard's contribution function
+ * (plot.py:63-79) once per Grid.
+ * Inputs dtaus[n_atm][n_layers][n_lam], spectra[n_atm][n_lam], T[n_atm][n_layers] are host
+ * arrays to upload, or NULL for the device state the last frei_run_batch_ex(keep_dtaus) left
+ * (the kept dtaus, the rows F_up[n_layers-1], the final temperatures); p_bar[n_layers],
+ * lam_cm[n_lam] (the array spectrum * lam_cm is formed with, core.py:397-399), and for cf
+ * nu[n_lam], ratio[n_layers], hcperk as in frei_contribution.
+ * Outputs:
+ *   sums[n_atm][3]  A = sum_j p_milne[j] w[j], B = sum_j w[j] with w[j] = spectrum[j] *
+ *                   lam_cm[j] (core.py:397-403: np.average(p_milne, weights=w) = A / B), and
+ *                   C = sum_j spectrum[j] * trapz_w[j] with frei_set_grid's weights
+ *                   (core.py:408-414: np.trapz(flux, lam)).  Summed in a fixed order without
+ *                   atomics: bitwise the same from run to run.  The final interpolation and
+ *                   the fourth root stay on the host.
+ *   p_milne[n_atm][n_lam] (may be NULL): bitwise frei_milne_pressure's on the same dtaus.
+ *   cf[n_atm][n_layers][n_lam] (may be NULL: nothing is computed or allocated for it; T, nu
+ *                   and ratio are then unused): bitwise frei_contribution's.
+ * Fails with "no device dtaus" when an input is NULL and no kept dtaus are valid, and on a
+ * context from frei_ctx_create (use frei_milne_pressure / frei_contribution there).
+ */
+int frei_post_batch(frei_ctx* ctx, const double* dtaus, const double* spectra, const double* T,
+                    const double* p_bar, const double* lam_cm, const double* nu,
+                    const double* ratio, double hcperk, double* sums, double* p_milne,
+                    double* cf);
+/* HIP-event milliseconds of the kernels of the last frei_milne_pressure, frei_contribution or
+ * frei_post_batch call on this context (uploads and read-backs excluded); 0 before any. */
+int frei_post_timing(frei_ctx* ctx, double* ms);
 
 /* Which sweep implementation the context's current tables select (after metadata build):
  * bit 0 fast path (on-node pressures, >= 2 T nodes, S <= 8), bit 1 step table staged in
