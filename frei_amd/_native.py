@@ -52,6 +52,9 @@ SIGNATURES = {
                                                 ctypes.c_int, _dp, ctypes.c_int]),
     "frei_set_mmr": (ctypes.c_int, [_vp, _dp]),
     "frei_set_chemistry": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_int, _dp, ctypes.c_int]),
+    "frei_set_chemistry_batch": (ctypes.c_int, [_vp, _dp, ctypes.c_int,
+                                                ctypes.POINTER(ctypes.c_int32), _dp,
+                                                ctypes.c_int, _dp, ctypes.c_int]),
     "frei_set_fluxes": (ctypes.c_int, [_vp, _dp, _dp]),
     "frei_get_fluxes": (ctypes.c_int, [_vp, _dp, _dp]),
     "frei_get_spectrum": (ctypes.c_int, [_vp, _dp]),

@@ -14,7 +14,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
-from .chemistry import chemistry
+from .chemistry import ChemistryTable, chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, SIGMA_SB, UM
 from .engine import EMIT, Engine, f_toa, planck_prefactor, trapz_weights
 from .opacity import sigma_scattering
@@ -23,11 +23,58 @@ from .units import scalar, value
 __all__ = ["BatchEngine", "BatchRecord", "BatchResult", "batched_emission_spectra"]
 
 
+def chemistry_tables(mmr, n_atm):
+    """``mmr`` as chemistry tables of a batch: None when it holds no :class:`ChemistryTable`,
+    else ``(tables, atm_tab)`` — the distinct tables (by identity, in order of first use) and
+    the table index of every atmosphere.  One table serves every atmosphere; a sequence names
+    one per atmosphere.  Tables and arrays cannot be mixed."""
+    if isinstance(mmr, ChemistryTable):
+        return [mmr], np.zeros(n_atm, dtype=np.int32)
+    if not isinstance(mmr, (list, tuple)) or not any(isinstance(x, ChemistryTable) for x in mmr):
+        return None
+    if not all(isinstance(x, ChemistryTable) for x in mmr):
+        raise ValueError("a batch takes ChemistryTables or mixing-ratio arrays, not a mix of both")
+    if len(mmr) != n_atm:
+        raise ValueError(f"{len(mmr)} chemistry tables for {n_atm} atmospheres")
+    tables, atm_tab = [], np.empty(n_atm, dtype=np.int32)
+    for m, t in enumerate(mmr):
+        k = next((i for i, u in enumerate(tables) if u is t), len(tables))
+        if k == len(tables):
+            tables.append(t)
+        atm_tab[m] = k
+    return tables, atm_tab
+
+
+def check_chemistry_nodes(tables):
+    """ValueError unless the chemistry tables share their nodes: a batch interpolates every
+    table on one (T, p) grid."""
+    t0 = tables[0]
+    for t in tables[1:]:
+        if not (np.array_equal(t.temperature, t0.temperature) and
+                np.array_equal(t.pressure, t0.pressure)):
+            raise ValueError("the chemistry tables of a batch must share their temperature and "
+                             "pressure nodes")
+
+
+def stack_chemistry(tables, names):
+    """values [n_tab][n_species][n_T][n_p] of chemistry tables on shared nodes."""
+    check_chemistry_nodes(tables)
+    return N.f64(np.array([t.array(names) for t in tables]))
+
+
 class BatchEngine:
     """``n_atm`` atmospheres on ``device``: ``g`` [n_atm] (cm s^-2), ``mmr``
     [n_atm][n_species][n_layers], ``F_toa`` [n_lam] shared or [n_atm][n_lam] per atmosphere;
     wavelengths, pressures (bar, descending), opacities and m_bar are shared (as in a grid of
-    Planets that differ in T, g, metallicity and irradiation)."""
+    Planets that differ in T, g, metallicity and irradiation).
+
+    ``mmr`` may also be T-dependent chemistry: one :class:`~frei_amd.chemistry.ChemistryTable`
+    for every atmosphere, or a sequence of ``n_atm`` of them on shared nodes (a metallicity axis:
+    one equilibrium table per [M/H]; the same object may serve several atmospheres and is
+    uploaded once).  The device re-interpolates each atmosphere's table at its own layer
+    temperatures every sweep (frei_set_chemistry_batch) and the species sum stays in the sweep.
+    Consecutive atmospheres in the same T brackets share table rows in the tiled sweep
+    (``FREI_ATM_TILE``), so order such a batch by temperature."""
 
     def __init__(self, lam_um, p_bar, opacities, g, mmr=None, m_bar=M_BAR_DEFAULT, F_toa=None,
                  device=0):
@@ -66,13 +113,44 @@ class BatchEngine:
         # tables: the single-atmosphere engine's upload paths (shared by every atmosphere)
         for s, name in enumerate(self.names):
             Engine._set_table(self, s, opacities[name], slice(0, self.n_lam))
-        if mmr is None:
-            T0 = np.full(self.n_layers, 1000.0)
-            mm = chemistry(T0, self.p_bar, self.names, m_bar=self.m_bar)
-            mmr = np.array([mm[nm] for nm in self.names])
-        self.mmr = N.f64(np.broadcast_to(np.asarray(mmr, dtype=float),
-                                         (self.n_atm, len(self.names), self.n_layers)))
-        N.check(lib.frei_set_mmr(ctx, N.dptr(self.mmr)))
+        try:
+            chem = chemistry_tables(mmr, self.n_atm)
+            if mmr is None or chem is not None:
+                T0 = np.full(self.n_layers, 1000.0)
+                mm = chemistry(T0, self.p_bar, self.names, m_bar=self.m_bar)
+                mmr = np.array([mm[nm] for nm in self.names])
+            self.mmr = N.f64(np.broadcast_to(np.asarray(mmr, dtype=float),
+                                             (self.n_atm, len(self.names), self.n_layers)))
+            N.check(lib.frei_set_mmr(ctx, N.dptr(self.mmr)))
+            self.chemistry = None
+            if chem is not None:   # T-dependent chemistry, re-evaluated on the device every sweep
+                self.set_chemistry(*chem)
+        except BaseException:
+            self.close()
+            raise
+
+    def set_chemistry(self, tables, atm_tab=None):
+        """Chemistry tables of the batch (frei_set_chemistry_batch): ``tables`` a list of
+        :class:`~frei_amd.chemistry.ChemistryTable` on shared nodes, atmosphere m reads
+        ``tables[atm_tab[m]]`` (default: table 0).  ``tables=None`` returns to the fixed
+        mixing ratios and the contracted path."""
+        lib = N.lib()
+        if tables is None:
+            N.check(lib.frei_set_chemistry_batch(self._ctx, None, 0, None, None, 0, None, 0))
+            self.chemistry = None
+            return
+        tables = list(tables)
+        atm = np.ascontiguousarray(np.zeros(self.n_atm) if atm_tab is None else atm_tab,
+                                   dtype=np.int32)
+        if atm.shape != (self.n_atm,):
+            raise ValueError(f"atm_tab must have {self.n_atm} entries")
+        v = stack_chemistry(tables, self.names)
+        t0 = tables[0]
+        N.check(lib.frei_set_chemistry_batch(
+            self._ctx, N.dptr(v), len(tables), atm.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            N.dptr(N.f64(t0.temperature)), t0.temperature.size, N.dptr(N.f64(t0.pressure * BAR)),
+            t0.pressure.size))
+        self.chemistry = (tables, atm)
 
     def close(self):
         if getattr(self, "_ctx", None):
@@ -257,6 +335,34 @@ class BatchResult(list):
         self.close()
 
 
+def grid_mixing_ratios(grids, names):
+    """The ``mmr`` argument of :class:`BatchEngine` for a list of Grids: the list of their
+    ChemistryTables when every grid carries one, else the array [n_atm][n_species][n_layers] of
+    their fixed mixing ratios (the mock where a grid has none).  A grid with a chemistry
+    provider, or tables on some grids and arrays on others, is a ValueError."""
+    for gr in grids:
+        if getattr(gr, "chemistry", None) is not None:
+            raise ValueError("a batch cannot step a chemistry provider: tabulate it as a "
+                             "ChemistryTable on (T, p) nodes and load it with mmr=")
+    is_tab = [isinstance(gr.mmr, ChemistryTable) for gr in grids]
+    if all(is_tab):
+        check_chemistry_nodes(chemistry_tables([gr.mmr for gr in grids], len(grids))[0])
+        return [gr.mmr for gr in grids]
+    if any(is_tab):
+        raise ValueError("batched grids must all carry ChemistryTables or all carry fixed "
+                         "mixing ratios, not a mix of both")
+    mmrs = []
+    for gr in grids:
+        if gr.mmr is not None:
+            mmrs.append(np.broadcast_to(np.asarray(gr.mmr, dtype=float),
+                                        (len(names), gr.pressures.size)))
+        else:
+            mm = chemistry(np.full(gr.pressures.size, 1000.0), gr.pressures, names,
+                           m_bar=gr.planet.m_bar)
+            mmrs.append(np.array([mm[n] for n in names]))
+    return np.array(mmrs)
+
+
 def batched_emission_spectra(grids, n_timesteps=1, n_zero_crossings=2, convergence_dT=3.0,
                              device=0, post=False):
     """Grid.emission_spectrum for a list of Grids that share wavelengths, pressures and
@@ -274,15 +380,7 @@ def batched_emission_spectra(grids, n_timesteps=1, n_zero_crossings=2, convergen
         if gr.planet.alpha != g0.planet.alpha or gr.planet.m_bar != g0.planet.m_bar:
             raise ValueError("batched grids must share alpha and m_bar")
     names = list(g0.opacities)
-    mmrs = []
-    for gr in grids:
-        if gr.mmr is not None:
-            mmrs.append(np.broadcast_to(np.asarray(gr.mmr, dtype=float),
-                                        (len(names), gr.pressures.size)))
-        else:
-            mm = chemistry(np.full(gr.pressures.size, 1000.0), gr.pressures, names,
-                           m_bar=gr.planet.m_bar)
-            mmrs.append(np.array([mm[n] for n in names]))
+    mmr = grid_mixing_ratios(grids, names)
     pl = g0.planet
     # each planet's own irradiation (core.py:262): one F_TOA per atmosphere when they differ
     ft = np.array([F_TOA(g0.lam, T_star=gr.planet.T_star, a_rstar=gr.planet.a_rstar)
@@ -290,7 +388,7 @@ def batched_emission_spectra(grids, n_timesteps=1, n_zero_crossings=2, convergen
     if all(np.array_equal(f, ft[0]) for f in ft[1:]):
         ft = ft[0]
     eng = BatchEngine(g0.lam, g0.pressures, g0.opacities, [gr.planet.g for gr in grids],
-                      mmr=np.array(mmrs), m_bar=pl.m_bar, F_toa=ft, device=device)
+                      mmr=mmr, m_bar=pl.m_bar, F_toa=ft, device=device)
     T_init = np.array([gr.init_temperatures for gr in grids])
     if post:
         try:

@@ -202,6 +202,10 @@ struct ChemArgs {
   const int32_t* pj;       // [n_layers] pressure bracket of each layer (node index)
   const double* pz;        // [n_layers] weight of node pj + 1 (log10 p)
   int n_T, n_p;
+  // batched contexts (frei_set_chemistry_batch): tab holds n_tab tables of tab_stride elements
+  // and atmosphere m reads table atm_tab[m] (nullptr: one table, atm_view leaves tab alone)
+  const int32_t* atm_tab;  // [n_atm]
+  int64_t tab_stride;      // n_species * n_T * n_p
 };
 
 // Bracket of x on ascending nodes g[n] clamped to [g0, g_{n-1}]: node i <= n - 2 and the
@@ -415,6 +419,14 @@ __host__ __device__ inline int64_t part_at(int idx, int bx, int nbx, int ns4) {
 void launch_sweep(int dir, const SweepArgs& a, int nblocks, bool fast, hipStream_t st);
 void launch_sweep_fast(int dir, int S, int depth, int pf, bool nan_check, bool shared,
                        const FastArgs& a, int nblocks, hipStream_t st);
+// The atmosphere-tiled per-species sweep of a batched chemistry context: one block sweeps one
+// 256-wavelength block for AT = 2 or 4 consecutive atmospheres in lockstep and loads the 2 S
+// table rows of a step once for consecutive atmospheres whose records carry the same row offset.
+// Shared-bracket records (a.ssteps, read from global memory), S in [2, 8], staged partial sums
+// (a.red_rows = 2); nblocks wavelength blocks x ceil(n_atm / AT) tiles.  Fluxes and partial sums
+// bitwise those of launch_sweep_fast(S, depth 2) over (block, atmosphere).
+void launch_sweep_tile(int dir, int S, int AT, const FastArgs& a, int nblocks, hipStream_t st);
+size_t tile_lds_bytes(int AT, int ns);
 // The contracted one-lane sweep with two adjacent wavelengths per lane (even n_lam, global step
 // records, staged partial sums: a.red_rows = 2); nblocks = ceil(n_lam / (2 kBlock)).
 void launch_sweep_pair(int dir, const FastArgs& a, int nblocks, hipStream_t st);

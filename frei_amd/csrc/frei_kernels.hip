@@ -974,6 +974,247 @@ __global__ __launch_bounds__(kBlock, 1) void sweep_fast_kernel(
                                                          blockIdx.x, gridDim.x);
 }
 
+// ---------------------------------------------------------------- K1, atmosphere-tiled form
+// Batched contexts with T-dependent chemistry (frei_set_chemistry_batch): the species sum stays
+// in the sweep, so every atmosphere reads the same shared per-species tables, and two
+// atmospheres whose layer i sits in the same T bracket read the same 2 S rows.  One block sweeps
+// one 256-wavelength block for AT consecutive atmospheres in lockstep, one lane per wavelength,
+// every atmosphere's carried flux and Planck value in registers: the (step, atmosphere) pairs
+// run step-major, and a pair loads the 2 S rows only when its record's row offset (wave-uniform,
+// a scalar compare) differs from that of the rows in registers — the pair before it.
+// Atmospheres ordered so that neighbours share brackets (a sweep over T_ref, gravity,
+// metallicity sorted by T_ref) load each row set once per tile instead of once per atmosphere.
+//
+// Loads in flight: once a pair's opacity sum has consumed the rows, the next pair's rows (when
+// they differ) and its stale opposite-stream flux are issued, and land behind this pair's
+// coefficients and flux update — sweep_fast_body's refill-after-use with a distance of one pair;
+// every wait sits at the top of a pair, where both are needed.
+//
+// Per atmosphere the arithmetic is sweep_fast_body's per-species form (mmr[s] (vlo wlo + vhi whi)
+// summed over s in order, then the same step functions), and each step's four weighted values
+// are summed over the wave with the staged tree of red_rows = 2 (8 lanes of a row in order, then
+// three DPP levels) and over the block's four waves in the epilogue: fluxes and partial sums are
+// bitwise those of sweep_fast_kernel over (block, atmosphere).  Each atmosphere honours its own
+// convergence flag (skipped while the rest of its tile runs); no atomics, no waits on another
+// workgroup.  Step records are read from global memory through the scalar cache: AT records per
+// step, against 2 S row loads per lane (staging AT step tables in LDS would halve the blocks
+// per CU at AT = 4 for loads the scalar cache already serves).
+__host__ __device__ inline int64_t tile_red_doubles(int AT, int ns) {
+  return (int64_t)AT * (kBlock / 64) * ns * 4;
+}
+size_t tile_lds_bytes(int AT, int ns) {
+  return (size_t)(tile_red_doubles(AT, ns) + (kBlock / 64) * 4 * kStageRow) * sizeof(double);
+}
+
+template <int DIR, int S, int AT>
+__global__ __launch_bounds__(kBlock) void sweep_tile_kernel(FastArgs a) {
+  static_assert(S >= 2 && S <= kMaxFastS, "per-species tables (NaN-free: scanned at load)");
+  static_assert(AT == 2 || AT == 4, "tile of 2 or 4 atmospheres");
+  extern __shared__ double red[];   // [AT][wave][step][4], then the per-wave stage tile
+  const int m0 = blockIdx.y * AT;
+  const int bx = blockIdx.x, nbx = gridDim.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = tid >> 6;
+  const int ns = a.n_steps;
+  const int64_t nl = a.n_lam;
+  // the tile's running atmospheres: inside the batch (the last tile may be partial) and not
+  // converged; nx[t]: the next running atmosphere after t (AT: none)
+  bool run[AT];
+  int nx[AT];
+  int first = AT;
+#pragma unroll
+  for (int t = AT - 1; t >= 0; --t) {
+    const int m = m0 + t;
+    run[t] = m < a.n_atm && (a.force || !a.conv[m]);
+    nx[t] = first;
+    if (run[t]) first = t;
+  }
+  if (first == AT) return;
+  const int64_t j0 = (int64_t)bx * kBlock + tid;
+  const bool act = j0 < nl;
+  const int64_t j = act ? j0 : nl - 1;
+  const double c1 = a.c1[j], hcl = a.hcl[j], sig = a.sig[j];
+  const double wt = act ? a.wtr[j] : 0.0;
+  double* stage = red + tile_red_doubles(AT, ns) + (int64_t)wv * 4 * kStageRow;
+  auto rec_of = [&](int t, int k) -> const FastStepS& {
+    return a.ssteps[(int64_t)(m0 + t) * a.bs.steps + k];
+  };
+  auto layer_of = [&](int k) { return step_layer(DIR, k, ns + 1); };
+  auto top_of = [&](int k) { return DIR == kEmit && k == ns - 1; };
+  auto load_rows = [&](int64_t off, double (&v)[2 * S], double dep) {
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const double* r = a.tab[s] + after_use(off + j, dep);
+      v[2 * s] = *(r);
+      v[2 * s + 1] = *(r + a.pitch);
+    }
+  };
+  auto load_stale = [&](int t, int k) {
+    const int i = layer_of(k);
+    const int64_t fo = (int64_t)(m0 + t) * a.bs.flux;
+    const double* src =
+        (DIR == kEmit) ? (top_of(k) ? a.ftoa + (int64_t)(m0 + t) * a.bs.ftoa
+                                    : a.F_down + fo + (int64_t)(i + 1) * nl)
+                       : a.F_up + fo + (int64_t)i * nl;
+    return src[j];
+  };
+  double carry[AT], Bc[AT];
+#pragma unroll
+  for (int t = 0; t < AT; ++t) {
+    carry[t] = Bc[t] = 0.0;
+    if (!run[t]) continue;
+    const int64_t fo = (int64_t)(m0 + t) * a.bs.flux;
+    const int l0 = layer_of(0);
+    const FastStepS& r0 = rec_of(t, 0);
+    if (DIR == kEmit) {
+      carry[t] = a.F_up[fo + (int64_t)l0 * nl + j];
+      Bc[t] = planck(c1, hcl, r0.iT1);
+    } else {
+      carry[t] = a.F_down[fo + (int64_t)(l0 + 1) * nl + j];
+      Bc[t] = planck(c1, hcl, r0.iT2);
+    }
+  }
+  double v[2 * S];
+  int64_t cur_off = rec_of(first, 0).off;
+  load_rows(cur_off, v, 0.0);
+  double sb = load_stale(first, 0);
+  ring_fence();
+  for (int k = 0; k < ns; ++k) {
+    progress_priority(k, ns);
+    const int i = layer_of(k);
+    const bool top = top_of(k);
+#pragma unroll
+    for (int t = 0; t < AT; ++t) {
+      if (!run[t]) continue;   // wave-uniform
+      const FastStepS& rc = rec_of(t, k);
+      const int64_t fo = (int64_t)(m0 + t) * a.bs.flux;
+      // the step's new Planck value, then the species-summed opacity (opacity.py:250-269)
+      const double X = planck(c1, hcl, DIR == kEmit ? rc.iT2 : rc.iT1);
+      double tot = 0.0;
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        const double acc = v[2 * s] * rc.wlo + v[2 * s + 1] * rc.whi;
+        const double ops = rc.mmr[s] * acc;
+        tot = (s == 0) ? ops : tot + ops;
+      }
+      const double F_st = sb;
+      consume(F_st);
+      ring_fence();
+      // the next running pair: its rows when their offset differs from the ones just used, and
+      // its stale flux
+      {
+        const int tn = nx[t] < AT ? nx[t] : first;
+        const int kn = nx[t] < AT ? k : k + 1;
+        if (kn < ns) {
+          const int64_t off = rec_of(tn, kn).off;
+          if (off != cur_off) {
+            load_rows(off, v, tot);
+            cur_off = off;
+          }
+          sb = load_stale(tn, kn);
+        }
+      }
+      ring_fence();
+      // coefficients of the step (sweep_fast_body: coef, coefB with one step per block)
+      StepCoef c;
+      const double kap = tot + sig;
+      const double dtau = rc.dm * kap;
+      const double w0 = fm::div(sig, sig + kap);
+      double B1, B2;
+      if (DIR == kEmit) {
+        B1 = Bc[t];
+        B2 = top ? Bc[t] : X;
+        Bc[t] = B2;
+      } else {
+        B2 = Bc[t];
+        B1 = X;
+        Bc[t] = B1;
+      }
+      CoefHead h = coef_head_e1(w0, dtau, B1, B2);
+      if (!__all(!(w0 > 0.1))) {
+        ring_fence();
+        coef_head_general(w0, dtau, B1, B2, h);
+        ring_fence();
+      }
+      coef_tail<true>(w0, dtau, B1, B2, h.sq, h.r, h.q, h.pi_w, c);
+      // fluxes, stores, bolometric partials
+      double F1u, F2d;
+      if (DIR == kEmit) { F1u = carry[t]; F2d = F_st; } else { F2d = carry[t]; F1u = F_st; }
+      const double F2u = step_up(c.psi, c.xi, c.Xu, F1u, F2d);
+      const double F1d = step_dn(c.psi, c.xi, c.Xd, F1u, F2d);
+      if (act) {
+        const bool st_up = (DIR == kEmit) ? !top : (!a.live_only || i == 0);
+        const bool st_dn = (DIR == kAbsorb) || !a.live_only || top;
+        if (st_up) store_flux(a.F_up + fo + (int64_t)(i + 1) * nl + j, F2u);
+        if (st_dn) store_flux(a.F_down + fo + (int64_t)i * nl + j, F1d);
+        if (a.dtaus) a.dtaus[fo + (int64_t)(k + 1) * nl + j] = c.dtau;
+      }
+      carry[t] = (DIR == kEmit) ? F2u : F1d;
+      // the step's four sums over the wave's 64 lanes: the staged tree of red_rows = 2
+      stage[lane] = wt * F2u;
+      stage[kStageRow + lane] = wt * F2d;
+      stage[2 * kStageRow + lane] = wt * F1u;
+      stage[3 * kStageRow + lane] = wt * F1d;
+      __builtin_amdgcn_wave_barrier();
+      const int o = (lane >> 3) & 3;   // (the upper half-wave repeats the lower one's sums)
+      const double* r = stage + o * kStageRow + (lane & 7);
+      double y = r[0];
+#pragma unroll
+      for (int q = 1; q < 8; ++q) y += r[8 * q];
+      y += dpp_bcast<0xB1>(y);    // quad_perm [1,0,3,2]
+      y += dpp_bcast<0x4E>(y);    // quad_perm [2,3,0,1]
+      y += dpp_bcast<0x141>(y);   // row_half_mirror: the other quad of the 8-lane group
+      if (lane < 32 && (lane & 7) == 0)
+        red[(((int64_t)t * (kBlock / 64) + wv) * ns + k) * 4 + o] = y;
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < AT; ++t) {
+    if (!run[t]) continue;
+    const double* rt = red + (int64_t)t * (kBlock / 64) * ns * 4;
+    double* part = a.part + (int64_t)(m0 + t) * a.bs.part;
+    for (int idx = tid; idx < ns * 4; idx += kBlock) {
+      double s = rt[idx];
+      for (int w = 1; w < kBlock / 64; ++w) s += rt[(int64_t)w * ns * 4 + idx];
+      part[part_at(idx, bx, nbx, ns * 4)] = s;
+    }
+  }
+}
+
+static size_t sweep_shm(const void* kernel, const FastArgs& a, size_t shm);
+template <int DIR, int S, int AT>
+static void launch_tile_t(const FastArgs& a, int nblocks, hipStream_t st) {
+  const auto kernel = sweep_tile_kernel<DIR, S, AT>;
+  hipLaunchKernelGGL(kernel, dim3(nblocks, (a.n_atm + AT - 1) / AT), dim3(kBlock),
+                     sweep_shm(reinterpret_cast<const void*>(kernel), a,
+                               tile_lds_bytes(AT, a.n_steps)),
+                     st, a);
+}
+template <int DIR, int AT>
+static void launch_tile_s(int S, const FastArgs& a, int nblocks, hipStream_t st) {
+  switch (S) {
+    case 2: return launch_tile_t<DIR, 2, AT>(a, nblocks, st);
+    case 3: return launch_tile_t<DIR, 3, AT>(a, nblocks, st);
+    case 4: return launch_tile_t<DIR, 4, AT>(a, nblocks, st);
+    case 5: return launch_tile_t<DIR, 5, AT>(a, nblocks, st);
+    case 6: return launch_tile_t<DIR, 6, AT>(a, nblocks, st);
+    case 7: return launch_tile_t<DIR, 7, AT>(a, nblocks, st);
+    default: return launch_tile_t<DIR, 8, AT>(a, nblocks, st);
+  }
+}
+void launch_sweep_tile(int dir, int S, int AT, const FastArgs& a, int nblocks, hipStream_t st) {
+  if (dir == kEmit) {
+    if (AT == 4) launch_tile_s<kEmit, 4>(S, a, nblocks, st);
+    else launch_tile_s<kEmit, 2>(S, a, nblocks, st);
+  } else {
+    if (AT == 4) launch_tile_s<kAbsorb, 4>(S, a, nblocks, st);
+    else launch_tile_s<kAbsorb, 2>(S, a, nblocks, st);
+  }
+}
+
 // ---------------------------------------------------------------- K1, grouped-lane form
 // Small slices (e.g. 62.5k lambda per GPU over 8 GPUs) leave about one wave per SIMD, and a
 // lone wave issues a vector instruction only every other slot.  This form spends Q = 2 or 4
@@ -2184,6 +2425,7 @@ __device__ inline void atm_view(SetupArgs& u, int m) {
   u.fsteps += m * u.bs.steps;
   u.ssteps += m * u.bs.steps;
   if (u.bs.g) u.g = u.bs.g[m];
+  if (u.chem.atm_tab) u.chem.tab += u.chem.atm_tab[m] * u.chem.tab_stride;   // its own table
 }
 
 __device__ inline void atm_view(UpdateArgs& a, int m) {

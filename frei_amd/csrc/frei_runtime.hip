@@ -271,6 +271,17 @@ struct frei_ctx {
   std::vector<double> chem_tab, chem_T, chem_logp;   // host copies (frei_kappa)
   double *d_chem_tab = nullptr, *d_chem_T = nullptr, *d_chem_pz = nullptr;
   int32_t* d_chem_pj = nullptr;
+  // batched contexts (frei_set_chemistry_batch): chem_ntab tables, atmosphere m reads table
+  // chem_atm[m] (empty: one table for the context, frei_set_chemistry)
+  int chem_ntab = 1;
+  std::vector<int32_t> chem_atm;
+  int32_t* d_chem_atm = nullptr;
+  // Atmosphere-tiled per-species sweep of a chemistry batch (sweep_tile_kernel): atmospheres
+  // per block, FREI_ATM_TILE 1 (one block per (wavelength block, atmosphere): the one-lane
+  // per-species sweep), 2, 4 or -1 = automatic; tile: the width the last metadata build chose
+  // (0: not a chemistry batch)
+  int atm_tile = -1;
+  int tile = 0;
   // P2P exchange over xGMI (frei_comm_p2p_*): own mailbox (uncached device memory), the
   // mapped mailboxes of every rank (own included) and the per-sweep sequence number
   double* d_mbox = nullptr;
@@ -370,6 +381,33 @@ bool lam2_static(const frei_ctx* c, int depth, int pf) {
 
 bool lam2_form(const frei_ctx* c);   // (below: fast_form)
 
+// Atmospheres per block of a chemistry batch's sweep (0: not a chemistry batch).  The tiled
+// kernel is instantiated for S = 2..8 and reduces with the staged sums of the one-lane sweep it
+// must equal bit for bit (two steps in flight, red_stage); its LDS (one partial-sum block per
+// atmosphere) must fit 64 KiB.  Anything else takes the one-lane per-species sweep over
+// (block, atmosphere).  Automatic: the widest tile that still leaves the launch one resident
+// round of blocks (four per CU) — measured at 32 x 100k lambda x 8 species, 4 atmospheres per
+// block run 1.54x and 2 run 1.32x the rate of 1 (profiles/r07/batch_chem/, DESIGN.md §3 "K1,
+// atmosphere-tiled"); a launch that a wider tile would leave with idle CUs was not measured
+// and keeps the narrower one.
+int atm_tile_width(const frei_ctx* c, bool shared_nodes) {
+  if (!(c->n_atm > 1 && c->chem_on)) return 0;
+  int t = c->atm_tile;
+  if (t < 0) {
+    const int64_t round = 4 * (int64_t)c->n_cu;
+    t = 1;
+    for (int w = 2; w <= 4; w *= 2)
+      if ((int64_t)c->nblocks * ((c->n_atm + w - 1) / w) >= round) t = w;
+  }
+  const int ns = c->nL - 1;
+  bool ok = c->fast && shared_nodes && c->S >= 2 && c->S <= kMaxFastS &&
+            sweep_depth(c, c->S) == 2 && c->red_stage && staged_sums_fit(ns);
+  for (int s = 0; s < c->S && ok; ++s) ok = !c->sp[s].has_nan;
+  if (!ok) return 1;
+  while (t > 1 && tile_lds_bytes(t, ns) > 64 * 1024) t /= 2;
+  return t;
+}
+
 template <typename Lap>
 int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   const int nL = c->nL, S = c->S;
@@ -395,9 +433,14 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   }
   c->eff = on ? 1 : 0;
   if (!on) {
-    if (batch)
+    // a chemistry batch (frei_set_chemistry_batch) contracts nothing and allocates no table,
+    // but its sweeps read the per-species tables through one bracket per step all the same
+    bool chem_batch = batch && c->chem_on && shared_fast;
+    for (int s = 0; s < S && chem_batch; ++s) chem_batch = !c->sp[s].has_nan;
+    if (batch && !chem_batch)
       return fail("a batched context needs tables on shared on-node p/T nodes without NaN "
-                  "(one contracted table per atmosphere)");
+                  "(one contracted table per atmosphere; chemistry batches need them too: "
+                  "every atmosphere reads the species' tables through one shared bracket)");
     return 0;
   }
   const Species& q0 = c->sp[0];
@@ -614,14 +657,18 @@ int build_meta(frei_ctx* c) {
   // step records from global memory (C5, 32 x 100k lambda: -9 % per step, profiles/r04/c5/)
   // (a batched context always has the contracted table without NaN, or fails in build_contracted)
   const int bdepth = sweep_depth(c, 1);
-  const bool lam2_batch = c->n_atm > 1 && lam2_static(c, bdepth, sweep_pf(c, true, 1, bdepth));
+  // (a chemistry batch has no contracted table: the per-species one-lane or tiled sweep)
+  const bool lam2_batch = c->n_atm > 1 && !c->chem_on &&
+                          lam2_static(c, bdepth, sweep_pf(c, true, 1, bdepth));
   const bool small = c->nblocks <= c->shared_max_blocks && !lam2_batch;
+  c->tile = atm_tile_width(c, shared != 0);
   // the LDS-staged step table plus one partial-sum row per wave must leave room for several
   // blocks per CU (deep atmospheres: > ~260 layers read the step table from global memory)
   const size_t ns_l = (size_t)nL - 1;
   const bool lds_fits =
       (size_t)(kBlock / 64) * ns_l * 4 * sizeof(double) + ns_l * sizeof(FastStepS) <= 64 * 1024;
   c->shared = (c->shared_mode == 1 || (c->shared_mode < 0 && small)) && lds_fits ? shared : 0;
+  if (c->tile > 1) c->shared = shared;   // the tiled sweep reads the shared-bracket records
   HIP_TRY(hipStreamSynchronize(c->stream));   // queued kernels may still read the metadata
   dfree(c->d_smeta);
   dfree(c->d_pmeta);
@@ -716,6 +763,13 @@ SetupArgs setup_args(frei_ctx* c) {
     u.chem.pz = c->d_chem_pz;
     u.chem.n_T = c->chem_nT;
     u.chem.n_p = c->chem_np;
+    const int64_t per = (int64_t)c->S * c->chem_nT * c->chem_np;
+    if (c->n_atm > 1 && !c->chem_atm.empty()) {   // atm_view picks each atmosphere's table
+      u.chem.atm_tab = c->d_chem_atm;
+      u.chem.tab_stride = per;
+    } else if (!c->chem_atm.empty()) {            // a batched context of one atmosphere
+      u.chem.tab += c->chem_atm[0] * per;
+    }
   }
   return u;
 }
@@ -1037,6 +1091,9 @@ int run_sweep(frei_ctx* c, const SweepOpts& o, bool defer = false) {
       ++c->n_chained;
     } else if (lam2) {
       launch_sweep_pair(o.dir, f, nb_run, c->stream);
+    } else if (c->tile > 1 && !c->eff && c->chem_on && c->shared && m.red_rows == 2) {
+      // a chemistry batch, c->tile atmospheres per block
+      launch_sweep_tile(o.dir, S_run, c->tile, f, c->nblocks, c->stream);
     } else {
       launch_sweep_fast(o.dir, S_run, depth, pf, nan_check && !c->eff, c->shared != 0, f,
                         c->nblocks, c->stream);
@@ -1221,7 +1278,7 @@ AtmStride atm_stride(frei_ctx* c) {
   b.fb = ns * 4;
   b.hist = (int64_t)c->hist_cap * 2 * nL;
   b.flux = nL * c->nlam;
-  b.tab = (int64_t)c->eff_stride;
+  b.tab = c->eff ? (int64_t)c->eff_stride : 0;   // (a chemistry batch: the shared tables)
   b.part = ns * 4 * (int64_t)(4 * c->nblocks);
   b.ftoa = c->ftoa_per_atm ? c->nlam : 0;
   b.g = c->d_g;
@@ -1264,7 +1321,7 @@ const char* const kOptionNames[] = {"prefetch_depth", "shared", "shared_max_bloc
                                     "quad_max_blocks", "red_rows", "red_stage", "group_q",
                                     "fused_update", "graph", "pipe", "pipe_pf", "pipe_min_blocks", "rec_sweep",
                                     "pipe_max_blocks", "prefetch_steps", "k7_mfma", "sweep_lds_kb", "group_waves", "chain",
-                                    "lam2", "tail", "lazy_k3", nullptr};
+                                    "lam2", "tail", "lazy_k3", "atm_tile", nullptr};
 int set_option(frei_ctx* c, const std::string& k, int v) {
   if (k == "prefetch_depth") c->prefetch_depth = v;
   else if (k == "shared") c->shared_mode = v < 0 ? -1 : (v ? 1 : 0);
@@ -1289,6 +1346,7 @@ int set_option(frei_ctx* c, const std::string& k, int v) {
   else if (k == "lam2") c->lam2 = v < 0 ? -1 : (v ? 1 : 0);
   else if (k == "tail") c->tail = v != 0;
   else if (k == "lazy_k3") c->lazy_k3 = v != 0;
+  else if (k == "atm_tile") c->atm_tile = (v == 1 || v == 2 || v == 4) ? v : -1;
   else if (k == "sweep_lds_kb") c->sweep_lds_kb = v < 0 ? 0 : (v > 160 ? 160 : v);
   else if (k == "prefetch_steps") c->prefetch_steps = v >= 16 ? 16 : v >= 8 ? 8 : v == 2 ? 2 : 0;
   else return fail("unknown option '" + k + "'");
@@ -1473,6 +1531,7 @@ int frei_ctx_destroy(frei_ctx* c) {
   dfree(c->d_chem_T);
   dfree(c->d_chem_pz);
   dfree(c->d_chem_pj);
+  dfree(c->d_chem_atm);
   dfree(c->d_ones);
   dfree(c->d_prow);
   double* dd[] = {c->d_c1, c->d_hcl, c->d_sig, c->d_ftoa, c->d_wtr, c->d_p, c->d_lnp,
@@ -1700,17 +1759,10 @@ int frei_set_ftoa_batch(frei_ctx* c, const double* f_toa) {
   return 0;
 }
 
-int frei_set_chemistry(frei_ctx* c, const double* values, const double* T_nodes, int n_T,
-                       const double* p_nodes, int n_p) {
-  if (!c) return fail("null argument");
-  if (!c->grid_set) return fail("frei_set_grid must be called first");
-  TRY(set_device(c));
-  if (!values) {   // back to the fixed per-layer mmr arrays
-    c->chem_on = false;
-    c->meta_dirty = true;
-    return 0;
-  }
-  if (c->n_atm > 1) return fail("a chemistry table is per atmosphere: not for batched contexts");
+// The chemistry tables of a context: n_tab tables values[n_tab][S][n_T][n_p] on shared nodes;
+// atm_tab[n_atm] names each atmosphere's table (nullptr: one table, frei_set_chemistry).
+static int set_chem_tables(frei_ctx* c, const double* values, int n_tab, const int32_t* atm_tab,
+                           const double* T_nodes, int n_T, const double* p_nodes, int n_p) {
   if (!T_nodes || !p_nodes || n_T < 1 || n_p < 1) return fail("chemistry table needs nodes");
   for (int k = 1; k < n_T; ++k)
     if (!(T_nodes[k] > T_nodes[k - 1])) return fail("chemistry T nodes must ascend");
@@ -1718,7 +1770,8 @@ int frei_set_chemistry(frei_ctx* c, const double* values, const double* T_nodes,
     if (!(p_nodes[k] > 0) || (k > 0 && !(p_nodes[k] > p_nodes[k - 1])))
       return fail("chemistry p nodes must be positive and ascend");
   const int nL = c->nL;
-  const size_t nv = (size_t)c->S * n_T * n_p;
+  const size_t nv = (size_t)n_tab * c->S * n_T * n_p;
+  HIP_TRY(hipStreamSynchronize(c->stream));   // no queued update still reads the old tables
   c->chem_tab.assign(values, values + nv);
   c->chem_T.assign(T_nodes, T_nodes + n_T);
   c->chem_logp.resize(n_p);
@@ -1731,6 +1784,8 @@ int frei_set_chemistry(frei_ctx* c, const double* values, const double* T_nodes,
   dfree(c->d_chem_T);
   dfree(c->d_chem_pj);
   dfree(c->d_chem_pz);
+  dfree(c->d_chem_atm);
+  c->chem_on = false;
   TRY(dalloc(&c->d_chem_tab, nv));
   TRY(dalloc(&c->d_chem_T, n_T));
   TRY(dalloc(&c->d_chem_pj, nL));
@@ -1739,12 +1794,56 @@ int frei_set_chemistry(frei_ctx* c, const double* values, const double* T_nodes,
   TRY(h2d(c->d_chem_T, c->chem_T.data(), n_T, c->stream));
   TRY(h2d(c->d_chem_pj, pj.data(), nL, c->stream));
   TRY(h2d(c->d_chem_pz, pz.data(), nL, c->stream));
+  c->chem_atm.clear();
+  if (atm_tab) {
+    c->chem_atm.assign(atm_tab, atm_tab + c->n_atm);
+    TRY(dalloc(&c->d_chem_atm, c->n_atm));
+    TRY(h2d(c->d_chem_atm, c->chem_atm.data(), c->n_atm, c->stream));
+  }
   HIP_TRY(hipStreamSynchronize(c->stream));
+  c->chem_ntab = n_tab;
   c->chem_nT = n_T;
   c->chem_np = n_p;
   c->chem_on = true;
-  c->meta_dirty = true;   // the species contraction (K3) no longer applies
+  c->meta_dirty = true;   // the species contraction (K3 / K7) no longer applies
   return 0;
+}
+
+int frei_set_chemistry(frei_ctx* c, const double* values, const double* T_nodes, int n_T,
+                       const double* p_nodes, int n_p) {
+  if (!c) return fail("null argument");
+  if (!c->grid_set) return fail("frei_set_grid must be called first");
+  TRY(set_device(c));
+  if (!values) {   // back to the fixed per-layer mmr arrays
+    c->chem_on = false;
+    c->meta_dirty = true;
+    return 0;
+  }
+  if (c->n_atm > 1) return fail("a chemistry table is per atmosphere: not for batched contexts");
+  return set_chem_tables(c, values, 1, nullptr, T_nodes, n_T, p_nodes, n_p);
+}
+
+int frei_set_chemistry_batch(frei_ctx* c, const double* values, int n_tab,
+                             const int32_t* atm_tab, const double* T_nodes, int n_T,
+                             const double* p_nodes, int n_p) {
+  if (!c) return fail("null argument");
+  if (!c->batch_api)
+    return fail("frei_set_chemistry_batch needs a context from frei_ctx_create_batch "
+                "(a single context takes frei_set_chemistry)");
+  if (!c->grid_set) return fail("frei_set_grid must be called first");
+  TRY(set_device(c));
+  if (!values) {   // back to frei_set_mmr's fixed arrays and the contracted path
+    c->chem_on = false;
+    c->meta_dirty = true;
+    return 0;
+  }
+  if (n_tab < 1) return fail("n_tab must be >= 1");
+  if (!atm_tab) return fail("null atm_tab");
+  for (int m = 0; m < c->n_atm; ++m)
+    if (atm_tab[m] < 0 || atm_tab[m] >= n_tab)
+      return fail("atm_tab[" + std::to_string(m) + "] = " + std::to_string(atm_tab[m]) +
+                  " is outside [0, n_tab)");
+  return set_chem_tables(c, values, n_tab, atm_tab, T_nodes, n_T, p_nodes, n_p);
 }
 
 int frei_set_gravity(frei_ctx* c, const double* g) {
@@ -2177,7 +2276,11 @@ int frei_kappa(frei_ctx* c, double T, double p, double* k, double* sigma) {
       int j;
       double z;
       chem_bracket(c->chem_logp.data(), c->chem_np, std::log10(p), j, z);
-      ChemArgs h{c->chem_tab.data(), c->chem_T.data(), nullptr, nullptr, c->chem_nT, c->chem_np};
+      // (a batched context of one atmosphere: its own table of the n_tab)
+      const size_t t0 = c->chem_atm.empty()
+                            ? 0 : (size_t)c->chem_atm[0] * c->S * c->chem_nT * c->chem_np;
+      ChemArgs h{c->chem_tab.data() + t0, c->chem_T.data(), nullptr, nullptr, c->chem_nT,
+                 c->chem_np};
       m = chem_mmr_at(h, s, j, z, T);
     }
     terms[s] = make_term(sm, pm, c->tnodes.data(), c->tperm.data(), m, T, 0);
@@ -2553,7 +2656,9 @@ int frei_ctx_path(frei_ctx* c, int* flags) {
   const FastForm m = fast_form(c, chain_ready(c));
   const int Q = m.Q, NC = m.NC;
   const bool lam2 = c->fast && m.lam2;
-  *flags = (c->fast ? 1 : 0) | (c->fast && c->shared ? 2 : 0) | (c->eff ? 4 : 0) |
+  const int tile = (c->fast && !c->eff) ? c->tile : 0;   // a chemistry batch's sweep
+  *flags = (tile << 12) |
+           (c->fast ? 1 : 0) | (c->fast && c->shared && tile <= 1 ? 2 : 0) | (c->eff ? 4 : 0) |
            (nan ? 8 : 0) | (NC == 0 && Q == 2 ? 16 : 0) | (NC == 0 && Q == 4 ? 32 : 0) |
            (NC << 6) | (lam2 ? 512 : 0) |
            (c->fast && NC > 0 && !chain_ready(c) && tail_blocks(c, (int)((c->nlam + 255) / 256)) > 0

@@ -136,10 +136,26 @@ int frei_set_mmr(frei_ctx* ctx, const double* mmr);
  * interpolated at its current (T_i, p_i) — linear in T and in log10 p, clamped to the nodes —
  * when the update kernel writes the next sweep's step table; the species sum then stays in
  * the sweep (no K3 contraction).  values = NULL returns to frei_set_mmr's fixed arrays.
- * Single-atmosphere contexts; call after frei_set_grid.
+ * Single-atmosphere contexts (batched ones: frei_set_chemistry_batch); call after frei_set_grid.
  */
 int frei_set_chemistry(frei_ctx* ctx, const double* values, const double* T_nodes, int n_T,
                        const double* p_nodes, int n_p);
+/* Batched contexts: n_tab chemistry tables values[n_tab][n_species][n_T][n_p] on shared
+ * ascending T_nodes (K) x p_nodes (dyn cm^-2); atmosphere m uses table atm_tab[m].
+ * Interpolation exactly as frei_set_chemistry (chem_mmr_at).  values = NULL: back to
+ * frei_set_mmr's fixed arrays and the contracted path.
+ * With chemistry on, the context builds and allocates no contracted table (frei_ctx_path reports
+ * contracted = 0): every atmosphere's sweep sums the species from the shared tables, which must
+ * be on shared on-node p/T nodes without NaN as for any batched context.  Consecutive
+ * atmospheres that sit in the same T brackets share table rows in the tiled sweep (option
+ * "atm_tile"), so order a grid sweep by temperature.  frei_run_batch(_ex), frei_state_init /
+ * frei_iterate, frei_get_dtaus_batch, frei_post_batch, frei_set_gravity and
+ * frei_set_ftoa_batch work unchanged.  Errors: a context from frei_ctx_create (use
+ * frei_set_chemistry), n_tab < 1, an atm_tab entry outside [0, n_tab), nodes that do not
+ * ascend.  Call after frei_set_grid. */
+int frei_set_chemistry_batch(frei_ctx* ctx, const double* values, int n_tab,
+                             const int32_t* atm_tab, const double* T_nodes, int n_T,
+                             const double* p_nodes, int n_p);
 
 /* Flux state [n_layers][n_lam] (this slice), caller layout row-major. */
 int frei_set_fluxes(frei_ctx* ctx, const double* up, const double* down);
@@ -274,7 +290,9 @@ int frei_post_timing(frei_ctx* ctx, double* ms);
  * contracted one-lane sweep (large slices: option "lam2"), bit 10 the producer/consumer sweep
  * runs its update as trailing workgroups of its own launch (option "tail"; loops without
  * per-sweep events), bit 11 lazy K3: the setup contracted no row, the two-wavelength sweeps
- * contract the rows their records reach first (option "lazy_k3"). */
+ * contract the rows their records reach first (option "lazy_k3"), bits 12-14: atmospheres per
+ * block of a chemistry batch's per-species sweep (frei_set_chemistry_batch: 1 the one-lane sweep
+ * over (wavelength block, atmosphere), 2 or 4 the atmosphere-tiled sweep; 0 otherwise). */
 int frei_ctx_path(frei_ctx* ctx, int* flags);
 
 /* Tuning knobs (also FREI_<NAME> in the environment at context creation): "precontract"
@@ -290,7 +308,11 @@ int frei_ctx_path(frei_ctx* ctx, int* flags);
  * own after the sweep; bitwise identical results), "lazy_k3" (1, the default: with the
  * two-wavelength sweep, K3 contracts no row at setup — each sweep contracts the (pressure row,
  * T node) rows its records reach for the first time, for its own wavelengths, with K3's sum;
- * 0: every row at setup; bitwise identical results). */
+ * 0: every row at setup; bitwise identical results), "atm_tile" (atmospheres per block of a
+ * chemistry batch's sweep, frei_set_chemistry_batch: 1 one block per (wavelength block,
+ * atmosphere), 2 or 4 consecutive atmospheres in lockstep, loading the table rows they share
+ * once; -1, the default: the widest of them that leaves the launch four blocks per CU; bitwise
+ * identical results). */
 int frei_set_option(frei_ctx* ctx, const char* name, int value);
 /* With the "graph" option on (default off), T-P iterations (frei_iterate, frei_run) are
  * replayed from a captured hipGraph of a few iterations when one rank runs with timing off:
