@@ -110,6 +110,10 @@ OUTRIGHT_TWINS = {
         "tests/test_gpu_parity.py::test_temperature_dependent_chemistry_matches_oracle[c1_strong]",
     "test_high_albedo_lanes_match_oracle":
         "tests/test_gpu_parity.py::test_high_albedo_lanes_match_oracle[1--2]",
+    "test_high_albedo_thin_layers_tiles_match_oracle":
+        "tests/test_gpu_batch_chemistry_edges.py::test_high_albedo_tiles_match_oracle_outright",
+    "test_layers_outside_the_table_ranges_match_oracle":
+        "tests/test_gpu_batch_chemistry_edges.py::test_high_albedo_tiles_match_oracle_outright",
 }
 
 
