@@ -14,6 +14,7 @@ from .core import (B_star, F_TOA, Grid, Planet, Spectrum, contribution_function,
 from .engine import Engine, balanced_edges, partition, trapz_weights
 from .opacity import (OpacityTable, SeparableTable, binned_opacity, kappa,
                       load_example_opacity, rayleigh_H2, rayleigh_He)
+from .stellar import StellarSpectra, binned_stellar_spectrum, get_binned_phoenix_spectrum
 from .tp import pressure_grid, temperature_grid
 from .twostream import BB, E, absorb, emit, propagate_fluxes
 
@@ -25,4 +26,5 @@ __all__ = ["Planet", "Grid", "Spectrum", "effective_temperature", "wavelength_gr
            "iso_to_mass", "pressure_grid", "temperature_grid", "propagate_fluxes", "emit",
            "absorb", "BB", "E", "Engine", "balanced_edges", "partition", "trapz_weights", "CrossSection",
            "BinnedTable", "open_cross_section", "contribution_function", "BatchEngine",
-           "batched_emission_spectra", "ChemistryTable", "BatchRecord", "BatchResult"]
+           "batched_emission_spectra", "ChemistryTable", "BatchRecord", "BatchResult",
+           "StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum"]

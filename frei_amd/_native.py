@@ -103,6 +103,11 @@ SIGNATURES = {
     "frei_set_table_binned": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _dp, _dp,
                                              _i64, _i64, _dp, ctypes.c_int, _dp,
                                              ctypes.c_int]),
+    "frei_sspec_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _dp, ctypes.c_int,
+                                         _i64, _dp]),
+    "frei_sspec_bin": (ctypes.c_int, [_vp, _dp, _i64, ctypes.c_int, _dp,
+                                      ctypes.POINTER(ctypes.c_int64), _ip, _dp]),
+    "frei_sspec_destroy": (ctypes.c_int, [_vp]),
 }
 
 _lib = None

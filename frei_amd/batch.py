@@ -383,7 +383,8 @@ def batched_emission_spectra(grids, n_timesteps=1, n_zero_crossings=2, convergen
     mmr = grid_mixing_ratios(grids, names)
     pl = g0.planet
     # each planet's own irradiation (core.py:262): one F_TOA per atmosphere when they differ
-    ft = np.array([F_TOA(g0.lam, T_star=gr.planet.T_star, a_rstar=gr.planet.a_rstar)
+    ft = np.array([F_TOA(g0.lam, T_star=gr.planet.T_star, a_rstar=gr.planet.a_rstar,
+                         F_star=getattr(gr.planet, "stellar_spectrum", None))
                    for gr in grids])
     if all(np.array_equal(f, ft[0]) for f in ft[1:]):
         ft = ft[0]

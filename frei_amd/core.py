@@ -27,9 +27,29 @@ def wavelength_grid(min_micron=0.5, max_micron=10, n_bins=500, lam=None):
     return lam, wl_bins, R
 
 
-def F_TOA(lam, T_star=5800.0, f=2 / 3, a_rstar=A_RSTAR_HOT_JUPITER):
-    """Irradiation at the top of the atmosphere, erg s^-1 cm^-3 (core.py:48-55)."""
-    return f_toa(value(lam, "um"), scalar(T_star, "K"), f, a_rstar)
+def F_TOA(lam, T_star=5800.0, f=2 / 3, a_rstar=A_RSTAR_HOT_JUPITER, F_star=None):
+    """Irradiation at the top of the atmosphere, erg s^-1 cm^-3 (core.py:48-55).  ``F_star``
+    ([n_lam], erg s^-1 cm^-3) is the star's surface flux on ``lam`` and takes the place of the
+    blackbody's ``pi * B_star(T_star, lam)``."""
+    if F_star is None:
+        return f_toa(value(lam, "um"), scalar(T_star, "K"), f, a_rstar)
+    F_star = checked_stellar_spectrum(F_star, len(value(lam, "um")))
+    return f * a_rstar ** -2 * 1 / (2 * np.pi) * F_star
+
+
+def checked_stellar_spectrum(F_star, n_lam=None):
+    """``F_star`` as a float array [n_lam] in erg s^-1 cm^-3; a non-finite value (a bin of the
+    grid that the binned spectrum does not cover) is refused."""
+    F_star = np.asarray(value(F_star, "erg / (s cm3)"), dtype=float)
+    if F_star.ndim != 1 or (n_lam is not None and F_star.shape != (n_lam,)):
+        raise ValueError("stellar spectrum must be [n_lam], one value per grid wavelength"
+                         f"{'' if n_lam is None else f' ({n_lam})'}, got shape {F_star.shape}")
+    bad = np.nonzero(~np.isfinite(F_star))[0]
+    if bad.size:
+        shown = ", ".join(str(k) for k in bad[:8]) + (", ..." if bad.size > 8 else "")
+        raise ValueError(f"stellar spectrum does not cover the grid: bins {shown} hold fewer "
+                         "than 2 points")
+    return F_star
 
 
 def B_star(T_star, lam):
@@ -38,14 +58,18 @@ def B_star(T_star, lam):
 
 
 class Planet:
-    """Planetary system (core.py:65-106). m_bar in g, g in cm s^-2, T_star in K."""
+    """Planetary system (core.py:65-106). m_bar in g, g in cm s^-2, T_star in K.
+    ``stellar_spectrum`` ([n_lam], erg s^-1 cm^-3) is the star's surface flux binned onto the
+    grid's wavelengths (``StellarSpectra.bin``); without it the star is a blackbody of T_star."""
 
-    def __init__(self, a_rstar, m_bar, g, T_star, alpha):
+    def __init__(self, a_rstar, m_bar, g, T_star, alpha, stellar_spectrum=None):
         self.a_rstar = float(a_rstar)
         self.m_bar = scalar(m_bar, "g")
         self.g = scalar(g, "cm / s2")
         self.T_star = scalar(T_star, "K")
         self.alpha = alpha
+        self.stellar_spectrum = (None if stellar_spectrum is None
+                                 else checked_stellar_spectrum(stellar_spectrum))
 
     @classmethod
     def from_hot_jupiter(cls):
@@ -140,7 +164,8 @@ class Grid:
             pl = self.planet
             self._engine = Engine(self.lam, self.pressures, self.opacities, g=pl.g,
                                   m_bar=pl.m_bar,
-                                  F_toa=F_TOA(self.lam, T_star=pl.T_star, a_rstar=pl.a_rstar),
+                                  F_toa=F_TOA(self.lam, T_star=pl.T_star, a_rstar=pl.a_rstar,
+                                              F_star=getattr(pl, "stellar_spectrum", None)),
                                   mmr=self.mmr, chemistry=self.chemistry, device=self.device)
         return self._engine
 

@@ -15,6 +15,8 @@
  *   frei_xsec_bin           frei/opacity.py:66-170     binned_opacity(...) (one species)
  *                           frei/interp.py:156-307     groupby_bins_agg / AggregateTrapz
  *   frei_set_table_binned   frei/core.py:198-231       Grid.load_opacities(species, path)
+ *   frei_sspec_bin          frei/phoenix.py:13-17,43-52 get_binned_phoenix_spectrum(...) after
+ *                                                      the download
  *
  * Conventions (all plain pointers and sizes, no framework types):
  *   - Units are cgs: wavelength cm, pressure dyn cm^-2, T K, flux erg s^-1 cm^-3,
@@ -399,6 +401,28 @@ int frei_xsec_timing(frei_xsec* x, int on, double* total_ms, int* n_calls);
 int frei_set_table_binned(frei_ctx* ctx, int s, frei_xsec* x, int mode, const double* wl_bins,
                           const double* lam, int64_t n_bins, int64_t lam_lo,
                           const double* T_nodes, int n_T, const double* p_nodes, int n_p);
+
+/*
+ * Stellar spectrum binning (phoenix.py:13-17, 43-52).  A frei_sspec is a library of model
+ * spectra on one shared wavelength axis: flux[n_spec][n_hi] float64 resident in HBM on
+ * wl_hi[n_hi] (um, strictly ascending).
+ */
+typedef struct frei_sspec frei_sspec;
+int frei_sspec_create(frei_sspec** out, int device, const double* flux, int n_spec,
+                      int64_t n_hi, const double* wl_hi);
+/*
+ * Bin every spectrum onto wl_bins[n_bins+1] (um, strictly ascending).  Bin k holds the points
+ * wl_bins[k] < wl <= wl_bins[k+1] (pandas.cut, right-closed, the last bin too); its value is
+ * the trapezoid integral over its points divided by their span (max - min).
+ * out[n_spec][n_bins] is aligned with the bins (NaN: bins of < 2 points); NULL leaves it on
+ * the device.  counts[n_bins] receives the points per bin (may be NULL).  form: 0 automatic
+ * (by mean points per non-empty bin), 1 one lane per bin, 2 one wave per bin (a group of 4 to
+ * 32 lanes per bin where the bins hold fewer points than a wave has lanes); *form_used and
+ * *kernel_ms (HIP events around the kernel only) may be NULL.
+ */
+int frei_sspec_bin(frei_sspec* s, const double* wl_bins, int64_t n_bins, int form,
+                   double* out, int64_t* counts, int* form_used, double* kernel_ms);
+int frei_sspec_destroy(frei_sspec* s);
 
 #ifdef __cplusplus
 }
