@@ -16,6 +16,7 @@ from .opacity import (OpacityTable, SeparableTable, binned_opacity, kappa,
                       load_example_opacity, rayleigh_H2, rayleigh_He)
 from .stellar import StellarSpectra, binned_stellar_spectrum, get_binned_phoenix_spectrum
 from .tp import pressure_grid, temperature_grid
+from .transit import level_radii
 from .twostream import BB, E, absorb, emit, propagate_fluxes
 
 __version__ = "0.1.0"
@@ -27,4 +28,5 @@ __all__ = ["Planet", "Grid", "Spectrum", "effective_temperature", "wavelength_gr
            "absorb", "BB", "E", "Engine", "balanced_edges", "partition", "trapz_weights", "CrossSection",
            "BinnedTable", "open_cross_section", "contribution_function", "BatchEngine",
            "batched_emission_spectra", "ChemistryTable", "BatchRecord", "BatchResult",
-           "StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum"]
+           "StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum",
+           "level_radii"]

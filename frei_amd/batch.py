@@ -18,6 +18,7 @@ from .chemistry import ChemistryTable, chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, SIGMA_SB, UM
 from .engine import EMIT, Engine, f_toa, planck_prefactor, trapz_weights
 from .opacity import sigma_scattering
+from .transit import default_radius, level_radii, transit_call
 from .units import scalar, value
 
 __all__ = ["BatchEngine", "BatchRecord", "BatchResult", "batched_emission_spectra"]
@@ -255,8 +256,19 @@ class BatchEngine:
             out["cf"] = cf
         return out
 
+    def transit(self, radii, R_star, dtaus=None, want_tau=False):
+        """Every atmosphere's transit depth (R_eff / R_star)^2 per wavelength, [n_atm][n_lam],
+        in one device launch (frei_transit): ``radii`` [n_atm][n_layers] (cm, each row from
+        :func:`frei_amd.transit.level_radii`), ``dtaus`` [n_atm][n_layers][n_lam] a host array,
+        or None for the dtaus the last ``run(keep_dtaus=True)`` left on the device.  Row m is
+        bitwise ``Engine.transit`` of atmosphere m.  ``want_tau`` also returns the slant optical
+        depths [n_atm][n_layers - 1][n_lam]: (depth, tau_slant)."""
+        depth, tau = transit_call(self, self.n_atm, radii, R_star, dtaus, want_tau)
+        return (depth, tau) if want_tau else depth
+
     def post_timing(self):
-        """HIP-event milliseconds of the last :meth:`post` call's kernels."""
+        """HIP-event milliseconds of the kernels of the last :meth:`post` or :meth:`transit`
+        call."""
         return Engine.post_timing(self)
 
     # fixed-work driver pieces (benchmarks)
@@ -309,9 +321,10 @@ class BatchResult(list):
     the batched engine (``engine``, with every atmosphere's dtaus on the device) until
     :meth:`close`, so per-atmosphere arrays are fetched only when asked for."""
 
-    def __init__(self, records, engine):
+    def __init__(self, records, engine, planets=None):
         super().__init__(records)
         self.engine = engine
+        self.planets = planets     # the grids' Planets, in the order of the records
         self._cf = None
 
     def dtaus(self, m):
@@ -324,6 +337,29 @@ class BatchResult(list):
         if self._cf is None:
             self._cf = self.engine.post(want_cf=True)["cf"]
         return self._cf[m]
+
+    def transmission(self, R_p=None, R_star=None, P_ref=None):
+        """Every atmosphere's transit depth (R_eff / R_star)^2 per wavelength, [n_atm][n_lam],
+        from the dtaus the run left on the device, in one launch (BatchEngine.transit).  ``R_p``
+        and ``R_star`` (cm or Quantities; scalars or one per atmosphere) default to each
+        Planet's; ``P_ref`` (bar) is the pressure R_p refers to (level 1 by default)."""
+        eng, A = self.engine, len(self)
+        planets = self.planets if self.planets is not None else [None] * A
+
+        def per_atm(x):
+            return [None] * A if x is None else list(np.broadcast_to(value(x, "cm"), (A,)))
+        Rp = [default_radius(x, pl, "R_p", "the planet's radius")
+              for x, pl in zip(per_atm(R_p), planets)]
+        Rs = [default_radius(x, pl, "R_star", "the star's radius")
+              for x, pl in zip(per_atm(R_star), planets)]
+        radii = np.array([level_radii(self[m].final_T, eng.p_bar, float(eng.g[m]), eng.m_bar,
+                                      Rp[m], P_ref) for m in range(A)])
+        if len(set(Rs)) == 1:
+            return eng.transit(radii, Rs[0])
+        # stars of different radii: the depth scales with 1 / R_star^2 (one division per value,
+        # as the device forms it)
+        area = eng.transit(radii, 1.0)
+        return np.array([area[m] / (Rs[m] * Rs[m]) for m in range(A)])
 
     def close(self):
         self.engine.close()
@@ -403,7 +439,7 @@ def batched_emission_spectra(grids, n_timesteps=1, n_zero_crossings=2, convergen
             [BatchRecord(Spectrum(out["spectra"][m], g0.lam), out["final_T"][m],
                          int(out["n_iter"][m]), out["temp_hist"][m], float(te["T_eff"][m]),
                          float(te["T_milne"][m]), float(te["T_planck"][m]))
-             for m in range(len(grids))], eng)
+             for m in range(len(grids))], eng, [gr.planet for gr in grids])
     try:
         out = eng.run(T_init, n_timesteps, n_zero_crossings, scalar(convergence_dT, "K"),
                       pl.alpha)

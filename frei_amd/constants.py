@@ -16,5 +16,8 @@ G_JUPITER = 2478.6519476149147        # cm s^-2
 M_BAR_HOT_JUPITER = 4.0142926168559996e-24  # g (== 2.4 * M_P)
 A_RSTAR_HOT_JUPITER = 6.450964670116429
 M_BAR_DEFAULT = 2.4 * M_P
+# the radii G_JUPITER and A_RSTAR_HOT_JUPITER are formed with (IAU 2015 nominal, equatorial)
+R_JUPITER = 7.1492e9                  # cm
+R_SUN = 6.957e10                      # cm
 
 FLUX_UNIT = "erg / (s cm3)"

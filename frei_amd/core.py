@@ -5,9 +5,11 @@
 """
 import numpy as np
 
-from .constants import A_RSTAR_HOT_JUPITER, G_JUPITER, M_BAR_HOT_JUPITER, SIGMA_SB, UM
+from .constants import (A_RSTAR_HOT_JUPITER, G_JUPITER, M_BAR_HOT_JUPITER, R_JUPITER, R_SUN,
+                        SIGMA_SB, UM)
 from .engine import Engine, f_toa
 from .tp import pressure_grid, temperature_grid
+from .transit import default_radius, level_radii
 from .twostream import BB
 from .units import scalar, value
 
@@ -60,9 +62,12 @@ def B_star(T_star, lam):
 class Planet:
     """Planetary system (core.py:65-106). m_bar in g, g in cm s^-2, T_star in K.
     ``stellar_spectrum`` ([n_lam], erg s^-1 cm^-3) is the star's surface flux binned onto the
-    grid's wavelengths (``StellarSpectra.bin``); without it the star is a blackbody of T_star."""
+    grid's wavelengths (``StellarSpectra.bin``); without it the star is a blackbody of T_star.
+    ``R_p`` and ``R_star`` (cm or Quantities) are the radii of planet and star: the defaults of
+    the transmission spectra (``Grid.transmission_spectrum``, ``BatchResult.transmission``)."""
 
-    def __init__(self, a_rstar, m_bar, g, T_star, alpha, stellar_spectrum=None):
+    def __init__(self, a_rstar, m_bar, g, T_star, alpha, stellar_spectrum=None, R_p=None,
+                 R_star=None):
         self.a_rstar = float(a_rstar)
         self.m_bar = scalar(m_bar, "g")
         self.g = scalar(g, "cm / s2")
@@ -70,12 +75,14 @@ class Planet:
         self.alpha = alpha
         self.stellar_spectrum = (None if stellar_spectrum is None
                                  else checked_stellar_spectrum(stellar_spectrum))
+        self.R_p = None if R_p is None else scalar(R_p, "cm")
+        self.R_star = None if R_star is None else scalar(R_star, "cm")
 
     @classmethod
     def from_hot_jupiter(cls):
         """M_J, R_J, m_bar = 2.4 m_p, g = g_J, T_star = 5800 K, a = 0.03 AU (core.py:92-106)."""
         return cls(a_rstar=A_RSTAR_HOT_JUPITER, m_bar=M_BAR_HOT_JUPITER, g=G_JUPITER,
-                   T_star=5800.0, alpha=1)
+                   T_star=5800.0, alpha=1, R_p=R_JUPITER, R_star=R_SUN)
 
 
 class Spectrum:
@@ -189,6 +196,19 @@ class Grid:
         """Contribution function of the last emission_spectrum (plot.py:63-79)."""
         return contribution_function(self, self._last_dtaus if dtaus is None else dtaus,
                                      final_temps)
+
+    def transmission_spectrum(self, final_temps, dtaus=None, R_p=None, R_star=None, P_ref=None):
+        """Transmission spectrum of the converged atmosphere: a :class:`Spectrum` whose ``flux``
+        is the transit depth (R_eff / R_star)^2 per wavelength (frei_transit; the reference has
+        no counterpart).  ``dtaus`` defaults to the last emission_spectrum's (its device copy is
+        used); ``R_p`` and ``R_star`` (cm or Quantities) default to the Planet's; ``P_ref``
+        (bar) is the pressure R_p refers to (by default level 1, ``pressures[1]``)."""
+        pl = self.planet
+        radii = level_radii(final_temps, self.pressures, pl.g, pl.m_bar,
+                            default_radius(R_p, pl, "R_p", "the planet's radius"), P_ref)
+        R_star = default_radius(R_star, pl, "R_star", "the star's radius")
+        eng, d = _post_engine(self, self._last_dtaus if dtaus is None else dtaus)
+        return Spectrum(eng.transit(radii, R_star, d), self.lam)
 
     def emission_dashboard(self, *args, **kwargs):
         raise NotImplementedError("plotting is out of scope for the MI355X engine (SURVEY.md §2)")

@@ -499,6 +499,15 @@ void launch_post_batch(const double* dtaus, const double* F_top, int64_t f_strid
                        const double* wtr, const double* nu, const double* ratio, double hcperk,
                        int nL, int64_t n, int n_atm, double* p_milne, double* cf, double* part,
                        double* sums, hipStream_t st);
+// K9 (frei_transit.hip): transit depth per (atmosphere, wavelength) from dtaus[n_atm][nL][n]
+// and the level radii radii[n_atm][nL]; w[n_atm][w_stride] holds every atmosphere's chord
+// weights as transit_build_weights lays them out (transit_weight_count(nL) doubles, built on the
+// host from one atmosphere's radii).  depth[n_atm][n]; tau[n_atm][nL - 1][n] may be null.
+int64_t transit_weight_count(int nL);
+void transit_build_weights(const double* radii, int nL, double* w);
+void launch_transit(const double* dtaus, const double* radii, const double* w, int64_t w_stride,
+                    double r_star, int nL, int64_t n, int n_atm, double* depth, double* tau,
+                    hipStream_t st);
 void launch_contract_batch(const double* const* tabs, int S, const double* mmr,
                            const int32_t* prow, int n_layers, int n_T, int64_t pitch,
                            int n_atm, int64_t tab_stride, double* eff, hipStream_t st);

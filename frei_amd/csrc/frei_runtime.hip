@@ -2639,6 +2639,56 @@ int frei_post_batch(frei_ctx* c, const double* dtaus, const double* spectra, con
   return rc;
 }
 
+int frei_transit(frei_ctx* c, const double* dtaus, const double* radii, double r_star,
+                 double* depth, double* tau_slant) {
+  if (!ready(c) || !radii || !depth) return fail("context not ready or null argument");
+  if (!(r_star > 0.0)) return fail("frei_transit: r_star must be > 0");
+  const size_t A = c->n_atm, nL = c->nL, n = c->nlam, per = nL * n;
+  for (size_t m = 0; m < A; ++m)
+    for (size_t k = 0; k + 1 < nL; ++k)
+      if (!(radii[m * nL + k + 1] > radii[m * nL + k]))
+        return fail("frei_transit: radii must be strictly ascending (atmosphere " +
+                    std::to_string(m) + ", level " + std::to_string(k + 1) + ")");
+  if (!dtaus && !(c->d_dtaus && (c->batch_api ? c->dtaus_batch_valid : c->dtaus_valid)))
+    return fail(c->batch_api
+                    ? "no device dtaus: run frei_run_batch_ex with keep_dtaus first, or pass dtaus"
+                    : "no device dtaus: run frei_run first or pass dtaus");
+  TRY(set_device(c));
+  // chord weights, once per call and atmosphere (wave-uniform in the kernel)
+  const size_t nw = (size_t)transit_weight_count(c->nL);
+  std::vector<double> w(A * nw);
+  for (size_t m = 0; m < A; ++m) transit_build_weights(radii + m * nL, c->nL, w.data() + m * nw);
+  double *u_dt = nullptr, *d_r = nullptr, *d_w = nullptr, *d_depth = nullptr, *d_tau = nullptr;
+  PostTimer tm;
+  int rc = 0;
+  if (dtaus && !(rc = dalloc(&u_dt, A * per))) rc = h2d(u_dt, dtaus, A * per, c->stream);
+  if (!rc) rc = dalloc(&d_r, A * nL);
+  if (!rc) rc = dalloc(&d_w, A * nw);
+  if (!rc) rc = dalloc(&d_depth, A * n);
+  if (!rc && tau_slant) rc = dalloc(&d_tau, A * (nL - 1) * n);
+  if (!rc) rc = h2d(d_r, radii, A * nL, c->stream);
+  if (!rc) rc = h2d(d_w, w.data(), A * nw, c->stream);
+  if (!rc) {
+    tm.begin(c->stream);
+    launch_transit(u_dt ? u_dt : c->d_dtaus, d_r, d_w, (int64_t)nw, r_star, c->nL, c->nlam,
+                   c->n_atm, d_depth, d_tau, c->stream);
+    if (hipGetLastError() != hipSuccess) rc = fail("transit kernel launch failed");
+    tm.end(c->stream);
+  }
+  auto d2h = [&](double* h, const double* d, size_t cnt) {
+    if (!rc && hipMemcpyAsync(h, d, cnt * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
+                   hipSuccess)
+      rc = fail("transit copy failed");
+  };
+  d2h(depth, d_depth, A * n);
+  if (tau_slant) d2h(tau_slant, d_tau, A * (nL - 1) * n);
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("transit kernel failed");
+  tm.read(c);
+  dfree(u_dt), dfree(d_r), dfree(d_w), dfree(d_depth), dfree(d_tau);
+  if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
+  return rc;
+}
+
 int frei_post_timing(frei_ctx* c, double* ms) {
   if (!c || !ms) return fail("null argument");
   *ms = c->post_ms;

@@ -18,6 +18,7 @@ from .chemistry import ChemistryTable, fixed_provider_mmr, provider_mmr
 from .chemistry import chemistry as mock_chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, UM
 from .opacity import SeparableTable, sigma_scattering, table_values
+from .transit import transit_call
 from .units import scalar, value
 
 EMIT, ABSORB = 0, 1
@@ -404,6 +405,15 @@ class Engine:
         N.check(N.lib().frei_contribution(self._ctx, N.dptr(d), N.dptr(nu), N.dptr(ratio),
                                           N.dptr(N.f64(T)), H * C / K_B, N.dptr(cf)))
         return cf
+
+    def transit(self, radii, R_star, dtaus=None, want_tau=False):
+        """Transit depth (R_eff / R_star)^2 of this slice's wavelengths (frei_transit) from the
+        level radii ``radii`` [n_layers] (cm, :func:`frei_amd.transit.level_radii`) and ``dtaus``
+        (host array) or, with None, the dtaus the last run left on the device.  ``want_tau``
+        also returns the slant optical depths [n_layers - 1][n_lam], row k = tangent level
+        k + 1: (depth, tau_slant)."""
+        depth, tau = transit_call(self, 1, radii, R_star, dtaus, want_tau)
+        return (depth[0], tau[0]) if want_tau else depth[0]
 
     def path(self):
         """Sweep implementation the tables select: dict(fast, lds_steps, contracted, nan)."""

@@ -279,8 +279,39 @@ int frei_post_batch(frei_ctx* ctx, const double* dtaus, const double* spectra, c
                     const double* p_bar, const double* lam_cm, const double* nu,
                     const double* ratio, double hcperk, double* sums, double* p_milne,
                     double* cf);
-/* HIP-event milliseconds of the kernels of the last frei_milne_pressure, frei_contribution or
- * frei_post_batch call on this context (uploads and read-backs excluded); 0 before any. */
+/*
+ * Transmission (transit-depth) spectrum of every atmosphere of the context, (R_eff / R_star)^2
+ * per wavelength, from the final emit's vertical optical depths (K9, one launch over
+ * (wavelength block, atmosphere)).  The reference has no counterpart; this is the definition.
+ * Layer 0 is the bottom, g and m_bar are constant, levels l = 1 .. n_layers - 1 sit at the
+ * pressures p_l and the virtual top level n_layers at p_{nL-1} p_{nL-2} / p_{nL-3} (Q3).
+ *   Shell l (1 <= l <= n_layers - 1) lies between levels l and l + 1; its vertical optical depth
+ *   is row l of dtaus (emit order, as frei_run returns them; under hydrostatic equilibrium
+ *   kappa rho dz of the shell).  Row 0 (the ones placeholder, Q12) is never read: layer 0 lies
+ *   below the opaque base.
+ *   radii[n_atm][n_layers], cm, radii[m][k] = r_{k+1}: the level radii, strictly ascending
+ *   (frei_amd.transit.level_radii forms them from T, p, g, m_bar, R_p and a reference pressure).
+ *   Chord weights, 1 <= i <= j <= n_layers - 1, built on the host once per call and atmosphere:
+ *     s(i, k) = sqrt((r_k - r_i) * (r_k + r_i)),
+ *     G[i][j] = 2 * (r_{j+1} + r_j) / (s(i, j+1) + s(i, j))     (= 2 ds_ij / dz_j, no cancellation)
+ *   tau_i   = sum_{j=i}^{nL-1} G[i][j] * dtaus[j], added in ascending j from the j = i term;
+ *   f_i     = -expm1(-tau_i), f_nL = 0;
+ *   A       = r_1 r_1 + sum_{i=1}^{nL-1} (f_i r_i + f_{i+1} r_{i+1}) * (r_{i+1} - r_i), ascending i;
+ *   depth   = A / (r_star * r_star).
+ * dtaus[n_atm][n_layers][n_lam] is a host array to upload, or NULL for the device copy the last
+ * frei_run / frei_run_batch_ex(keep_dtaus) left ("no device dtaus" when there is none).
+ * Outputs depth[n_atm][n_lam] and, unless NULL (nothing is allocated or written for it then),
+ * tau_slant[n_atm][n_layers - 1][n_lam], row k = tangent level k + 1.  n_atm = 1 on a context
+ * from frei_ctx_create; a wavelength-slice context gives its own columns (every column is
+ * independent).  NaN or inf in a column stays in that column; nothing is checked.  Results are
+ * bitwise reproducible and the same from a single and a batched context.  Errors: null radii or
+ * depth, radii not strictly ascending, r_star <= 0.
+ */
+int frei_transit(frei_ctx* ctx, const double* dtaus, const double* radii, double r_star,
+                 double* depth, double* tau_slant);
+/* HIP-event milliseconds of the kernels of the last frei_milne_pressure, frei_contribution,
+ * frei_post_batch or frei_transit call on this context (uploads and read-backs excluded); 0
+ * before any. */
 int frei_post_timing(frei_ctx* ctx, double* ms);
 
 /* Which sweep implementation the context's current tables select (after metadata build):

@@ -13,4 +13,5 @@ for d in "$@"; do
 done
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared -std=c++17 \
   -Iinclude "$@" frei_amd/csrc/frei_kernels.hip frei_amd/csrc/frei_runtime.hip \
-  frei_amd/csrc/frei_binning.hip frei_amd/csrc/frei_stellar.hip -o "$OUT" -ldl
+  frei_amd/csrc/frei_binning.hip frei_amd/csrc/frei_stellar.hip frei_amd/csrc/frei_transit.hip \
+  -o "$OUT" -ldl
