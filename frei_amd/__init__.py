@@ -12,6 +12,7 @@ from .core import (B_star, F_TOA, Grid, Planet, Spectrum, contribution_function,
                    effective_temperature,
                    effective_temperature_milne, effective_temperature_planck, wavelength_grid)
 from .engine import Engine, balanced_edges, partition, trapz_weights
+from .observe import Instrument
 from .opacity import (OpacityTable, SeparableTable, binned_opacity, kappa,
                       load_example_opacity, rayleigh_H2, rayleigh_He)
 from .stellar import StellarSpectra, binned_stellar_spectrum, get_binned_phoenix_spectrum
@@ -29,4 +30,4 @@ __all__ = ["Planet", "Grid", "Spectrum", "effective_temperature", "wavelength_gr
            "BinnedTable", "open_cross_section", "contribution_function", "BatchEngine",
            "batched_emission_spectra", "ChemistryTable", "BatchRecord", "BatchResult",
            "StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum",
-           "level_radii"]
+           "level_radii", "Instrument"]

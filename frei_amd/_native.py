@@ -109,6 +109,13 @@ SIGNATURES = {
     "frei_sspec_bin": (ctypes.c_int, [_vp, _dp, _i64, ctypes.c_int, _dp,
                                       ctypes.POINTER(ctypes.c_int64), _ip, _dp]),
     "frei_sspec_destroy": (ctypes.c_int, [_vp]),
+    "frei_obs_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _i64, _i64,
+                                       ctypes.POINTER(ctypes.c_int64),
+                                       ctypes.POINTER(ctypes.c_int64), _dp]),
+    "frei_obs_apply": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_int32), _dp, _dp, _dp,
+                                      ctypes.c_int, _dp, _dp, _ip, _dp]),
+    "frei_obs_destroy": (ctypes.c_int, [_vp]),
 }
 
 _lib = None

@@ -361,6 +361,27 @@ class BatchResult(list):
         area = eng.transit(radii, 1.0)
         return np.array([area[m] / (Rs[m] * Rs[m]) for m in range(A)])
 
+    def observe(self, instrument, kind="eclipse", depth=None, weighting=None, data=None,
+                sigma=None, R_p=None, R_star=None):
+        """Every atmosphere through ``instrument`` (:class:`~frei_amd.observe.Instrument`, K10)
+        -> obs [n_atm][K], or (obs, chi2 [n_atm]) with ``data`` and ``sigma`` [K].  ``kind``:
+        "flux" the channel means of the emergent flux, "eclipse" the secondary-eclipse depths
+        (band integral of F_p / band integral of F_star) (R_p / R_star)^2 — both read the
+        spectra where the run left them on the device — and "transit" the band-averaged transit
+        depths of ``depth`` [n_atm][n_lam] (default: :meth:`transmission` with these radii),
+        ``weighting`` "stellar" (the default with Planets) or "flat".  Stars are the Planets':
+        ``stellar_spectrum``, else ``pi * B_star(T_star)``, distinct ones uploaded once; the radii
+        (cm or Quantities, scalars or one per atmosphere) default to each Planet's."""
+        from .observe import observe
+        A = len(self)
+        planets = self.planets if self.planets is not None else [None] * A
+        x = None
+        if kind == "transit":
+            x = self.transmission(R_p=R_p, R_star=R_star) if depth is None else depth
+        return observe(instrument, kind, planets, self.engine.lam_um, x=x,
+                       engine=None if kind == "transit" else self.engine, weighting=weighting,
+                       data=data, sigma=sigma, R_p=R_p, R_star=R_star)
+
     def close(self):
         self.engine.close()
 

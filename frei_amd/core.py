@@ -210,6 +210,19 @@ class Grid:
         eng, d = _post_engine(self, self._last_dtaus if dtaus is None else dtaus)
         return Spectrum(eng.transit(radii, R_star, d), self.lam)
 
+    def observe(self, instrument, spectrum, kind="eclipse", data=None, sigma=None, R_p=None,
+                R_star=None):
+        """``spectrum`` (the :class:`Spectrum` of emission_spectrum or transmission_spectrum)
+        through ``instrument`` (:class:`~frei_amd.observe.Instrument`, K10) -> obs [K], or
+        (obs, chi2) with ``data`` and ``sigma`` [K].  ``kind``: "flux" the channel means,
+        "eclipse" (band integral of F_p / band integral of F_star) (R_p / R_star)^2, "transit"
+        the band-averaged transit depth weighted by the stellar flux.  The star is the Planet's
+        ``stellar_spectrum``, else ``pi * B_star(T_star)``; the radii default to the Planet's."""
+        from .observe import observe
+        return observe(instrument, kind, [self.planet], self.lam,
+                       x=np.asarray(getattr(spectrum, "flux", spectrum), dtype=float),
+                       data=data, sigma=sigma, R_p=R_p, R_star=R_star)
+
     def emission_dashboard(self, *args, **kwargs):
         raise NotImplementedError("plotting is out of scope for the MI355X engine (SURVEY.md §2)")
 

@@ -520,6 +520,19 @@ void launch_contract(const double* const* tabs, int S, const double* mmr, const 
 // Error reporting shared by the runtime and the binning module (frei_last_error()).
 int set_error(const std::string& msg);
 }  // namespace frei
+struct frei_ctx;
+namespace frei {
+// K10 (frei_observe.hip) reads a context's spectra where they lie: the emergent row
+// F_up[n_layers - 1] of atmosphere m is rows + m * stride, n_lam doubles on `device`, written
+// by work queued on `stream` (what frei_post_batch reads with spectra = NULL).
+struct CtxRows {
+  const double* rows;
+  int64_t stride, n_lam;
+  int n_atm, device;
+  hipStream_t stream;
+};
+int ctx_emergent_rows(frei_ctx* c, CtxRows* out);
+}  // namespace frei
 struct frei_xsec;
 namespace frei {
 // K6 (frei_binning.hip): bin one species into table rows d_tab + row_off[kp * n_T + kt].

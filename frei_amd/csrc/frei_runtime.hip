@@ -1392,6 +1392,19 @@ int check_comm(frei_ctx* c) {
 
 }  // namespace
 
+namespace frei {
+int ctx_emergent_rows(frei_ctx* c, CtxRows* out) {
+  if (!ready(c) || !c->d_Fu) return fail("context not ready");
+  out->rows = c->d_Fu + (size_t)(c->nL - 1) * c->nlam;
+  out->stride = (int64_t)c->nL * c->nlam;
+  out->n_atm = c->n_atm;
+  out->n_lam = c->nlam;
+  out->device = c->device;
+  out->stream = c->stream;
+  return 0;
+}
+}  // namespace frei
+
 // ==================================================================== C ABI
 extern "C" {
 

@@ -455,6 +455,53 @@ int frei_sspec_bin(frei_sspec* s, const double* wl_bins, int64_t n_bins, int for
                    double* out, int64_t* counts, int* form_used, double* kernel_ms);
 int frei_sspec_destroy(frei_sspec* s);
 
+/*
+ * Synthetic observations (K10): native-resolution spectra taken to the channels of an
+ * instrument and scored against data.  The reference has no counterpart; this is the definition.
+ * An instrument is n_chan channels on a native wavelength axis of n_lam points.  Channel k covers
+ * the contiguous native indices first[k] .. first[k] + count[k] - 1 and has one weight per
+ * covered index, stored back to back: weights[off_k + t], off_k the prefix sum of the counts.
+ * Channels may overlap, come in any order and hold zero weights.  Required (frei_obs_create
+ * checks it on the host before it touches a device, naming the channel): count[k] >= 1,
+ * 0 <= first[k], first[k] + count[k] <= n_lam, every weight finite and >= 0, every channel's
+ * weight sum > 0.  Plan and weights stay resident on `device` with the handle.
+ */
+typedef struct frei_obs frei_obs;
+int frei_obs_create(frei_obs** out, int device, int64_t n_lam, int64_t n_chan,
+                    const int64_t* first, const int64_t* count, const double* weights);
+/*
+ * Apply the instrument to x[n_atm][n_lam].  Optional libraries num[n_lib][n_lam] and
+ * den[n_lib][n_lam]; select[n_atm] is the library row of atmosphere m (NULL: row 0 for all;
+ * ignored without num and den); scale[n_atm] (NULL: 1).  With w = weights + off_k, i = first[k] + t:
+ *   N_mk = sum_t (w[t] * x[m][i]) * num[select_m][i]        (without num: w[t] * x[m][i])
+ *   D_mk = sum_t  w[t] * den[select_m][i]                    (without den: sum_t w[t])
+ *   obs[m][k] = scale_m * (N_mk / D_mk)
+ * and, with data[n_chan], sigma[n_chan] and chi2 given,
+ *   chi2[m] = sum_k ((obs[m][k] - data[k]) / sigma[k])^2;
+ * sigma[k] = +inf makes channel k contribute exactly 0, sigma[k] <= 0 or NaN is an error.
+ * x is a host array (uploaded for the call), or NULL with a context: the source is then the
+ * emergent row F_up[n_layers - 1] of every atmosphere, in place in the flux state (what
+ * frei_post_batch reads with spectra = NULL); that needs n_atm == the context's atmosphere
+ * count, n_lam == its n_lam and the same device.  (A context of a wavelength slice therefore
+ * does not fit an instrument on the whole axis: a channel may straddle slices.)
+ * form: 0 automatic (by the mean points per channel), 1 one lane per channel (its points in
+ * ascending t), 2 one group of 4 to 64 lanes per channel (lane l of G sums t = l, l + G, ... in
+ * order, the G sums combine in the xor butterfly G/2, ..., 1; G follows from the mean points per
+ * channel).  chi2: lane l of 64 sums k = l, l + 64, ..., then the butterfly 32, ..., 1.  No
+ * atomics and no contraction of products: every result is bitwise the same from call to call,
+ * and row m of a batched call is bitwise the call on that row alone.  NaN or inf in x reaches
+ * exactly the channels that cover it; nothing in x, num or den is checked.
+ * Outputs obs[n_atm][n_chan]; chi2[n_atm], *form_used and *kernel_ms (HIP events around the
+ * kernels only) may be NULL.  Errors (handle and context stay usable): null handle or obs, x and
+ * ctx both null, a select entry outside [0, n_lib), chi2 without data or sigma, bad sigma, a
+ * context of another shape or device.
+ */
+int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const double* num,
+                   const double* den, int n_lib, const int32_t* select, const double* scale,
+                   const double* data, const double* sigma, int form, double* obs, double* chi2,
+                   int* form_used, double* kernel_ms);
+int frei_obs_destroy(frei_obs* o);
+
 #ifdef __cplusplus
 }
 #endif
