@@ -43,6 +43,7 @@ SIGNATURES = {
     "frei_post_batch": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_double,
                                        _dp, _dp, _dp]),
     "frei_transit": (ctypes.c_int, [_vp, _dp, _dp, ctypes.c_double, _dp, _dp]),
+    "frei_emergent": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, ctypes.c_int, _dp, _dp]),
     "frei_post_timing": (ctypes.c_int, [_vp, _dp]),
     "frei_set_grid": (ctypes.c_int, [_vp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_double,
                                      ctypes.c_double]),

@@ -16,6 +16,7 @@ import numpy as np
 from . import _native as N
 from .chemistry import ChemistryTable, chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, SIGMA_SB, UM
+from .emergent import emergent_call, pick
 from .engine import EMIT, Engine, f_toa, planck_prefactor, trapz_weights
 from .opacity import sigma_scattering
 from .transit import default_radius, level_radii, transit_call
@@ -266,9 +267,18 @@ class BatchEngine:
         depth, tau = transit_call(self, self.n_atm, radii, R_star, dtaus, want_tau)
         return (depth, tau) if want_tau else depth
 
+    def emergent(self, T, mu=None, weights=None, dtaus=None, want_intensity=False):
+        """Every atmosphere's ray-traced emergent flux [n_atm][n_lam] in one device launch
+        (frei_emergent; pure absorption): ``T`` [n_atm][n_layers], ``dtaus``
+        [n_atm][n_layers][n_lam] a host array, or None for the dtaus the last
+        ``run(keep_dtaus=True)`` left on the device; ``mu``, ``weights`` and the return as
+        ``Engine.emergent``, intensities [n_atm][n_mu][n_lam].  Row m is bitwise
+        ``Engine.emergent`` of atmosphere m."""
+        return pick(*emergent_call(self, self.n_atm, T, mu, weights, dtaus, want_intensity))
+
     def post_timing(self):
-        """HIP-event milliseconds of the kernels of the last :meth:`post` or :meth:`transit`
-        call."""
+        """HIP-event milliseconds of the kernels of the last :meth:`post`, :meth:`transit` or
+        :meth:`emergent` call."""
         return Engine.post_timing(self)
 
     # fixed-work driver pieces (benchmarks)
@@ -360,6 +370,13 @@ class BatchResult(list):
         # as the device forms it)
         area = eng.transit(radii, 1.0)
         return np.array([area[m] / (Rs[m] * Rs[m]) for m in range(A)])
+
+    def emergent(self, mu=None, weights=None, want_intensity=False):
+        """Every atmosphere's ray-traced emergent flux [n_atm][n_lam] from each record's
+        ``final_T`` and the dtaus the run left on the device, in one launch
+        (BatchEngine.emergent: angles, weights and the return as there)."""
+        T = np.array([np.asarray(value(r.final_T, "K"), dtype=float) for r in self])
+        return self.engine.emergent(T, mu=mu, weights=weights, want_intensity=want_intensity)
 
     def observe(self, instrument, kind="eclipse", depth=None, weighting=None, data=None,
                 sigma=None, R_p=None, R_star=None):

@@ -5,13 +5,13 @@
 """
 import numpy as np
 
-from .constants import (A_RSTAR_HOT_JUPITER, G_JUPITER, M_BAR_HOT_JUPITER, R_JUPITER, R_SUN,
-                        SIGMA_SB, UM)
+from .constants import (A_RSTAR_HOT_JUPITER, FLUX_UNIT, G_JUPITER, M_BAR_HOT_JUPITER, R_JUPITER,
+                        R_SUN, SIGMA_SB, UM)
 from .engine import Engine, f_toa
 from .tp import pressure_grid, temperature_grid
 from .transit import default_radius, level_radii
 from .twostream import BB
-from .units import scalar, value
+from .units import scalar, unit_of, value, with_unit
 
 __all__ = ["Grid", "Planet", "Spectrum", "effective_temperature", "wavelength_grid", "F_TOA",
            "B_star", "contribution_function"]
@@ -209,6 +209,25 @@ class Grid:
         R_star = default_radius(R_star, pl, "R_star", "the star's radius")
         eng, d = _post_engine(self, self._last_dtaus if dtaus is None else dtaus)
         return Spectrum(eng.transit(radii, R_star, d), self.lam)
+
+    def emergent_spectrum(self, final_temps, dtaus=None, mu=None, weights=None,
+                          want_intensity=False):
+        """Ray-traced emission spectrum of the converged atmosphere: a :class:`Spectrum` whose
+        ``flux`` is ``2 pi sum_k weights[k] mu[k] I(mu[k])`` of the emergent intensities at the
+        viewing angles ``mu`` (frei_emergent, pure absorption; the reference has no counterpart),
+        in emission_spectrum's unit (a Quantity when ``final_temps`` is one).  ``dtaus`` defaults
+        to the last emission_spectrum's (its device copy is used); ``mu`` and ``weights`` default
+        to :func:`frei_amd.gauss_angles` (4).  ``want_intensity`` also returns the intensities
+        [n_mu][n_lam]: (spectrum, intensity); ``mu`` without ``weights`` returns them alone."""
+        eng, d = _post_engine(self, self._last_dtaus if dtaus is None else dtaus)
+        out = eng.emergent(final_temps, mu=mu, weights=weights, dtaus=d,
+                           want_intensity=want_intensity)
+        if mu is not None and weights is None:
+            return out
+        flux, inten = out if want_intensity else (out, None)
+        spec = Spectrum(flux, self.lam)
+        spec.flux = with_unit(spec.flux, unit_of(FLUX_UNIT, final_temps))
+        return (spec, inten) if want_intensity else spec
 
     def observe(self, instrument, spectrum, kind="eclipse", data=None, sigma=None, R_p=None,
                 R_star=None):

@@ -508,6 +508,13 @@ void transit_build_weights(const double* radii, int nL, double* w);
 void launch_transit(const double* dtaus, const double* radii, const double* w, int64_t w_stride,
                     double r_star, int nL, int64_t n, int n_atm, double* depth, double* tau,
                     hipStream_t st);
+// K11 (frei_emergent.hip): emergent intensities intensity[n_atm][n_mu][n] (may be null) and their
+// quadrature flux[n_atm][n] (may be null, with ck) from dtaus[n_atm][nL][n], the context's Planck
+// constants c1[n], hcl[n], iT[n_atm][nL + 1] = 1 / T_l (l = 1 .. nL; entry 0 unused, entry nL
+// repeats nL - 1), imu[n_mu] = 1 / mu[k] and ck[n_mu] = weights[k] mu[k], all on the device.
+void launch_emergent(const double* dtaus, const double* c1, const double* hcl, const double* iT,
+                     const double* imu, const double* ck, int n_mu, int nL, int64_t n, int n_atm,
+                     double* intensity, double* flux, hipStream_t st);
 void launch_contract_batch(const double* const* tabs, int S, const double* mmr,
                            const int32_t* prow, int n_layers, int n_T, int64_t pitch,
                            int n_atm, int64_t tab_stride, double* eff, hipStream_t st);

@@ -2702,6 +2702,77 @@ int frei_transit(frei_ctx* c, const double* dtaus, const double* radii, double r
   return rc;
 }
 
+int frei_emergent(frei_ctx* c, const double* dtaus, const double* T, const double* mu,
+                  const double* weights, int n_mu, double* intensity, double* flux) {
+  if (!ready(c) || !T || !mu) return fail("context not ready or null argument");
+  if (!intensity && !flux) return fail("frei_emergent: intensity and flux are both null");
+  if ((weights != nullptr) != (flux != nullptr))
+    return fail("frei_emergent: weights and flux must be both given or both null");
+  if (n_mu < 1 || n_mu > 64) return fail("frei_emergent: n_mu must be in [1, 64]");
+  const size_t A = c->n_atm, nL = c->nL, n = c->nlam, per = nL * n, K = (size_t)n_mu;
+  // 1 / mu[k], c_k = weights[k] mu[k] and 1 / T_l, formed here once per call (wave-uniform in
+  // the kernel); iT[m][nL] is the virtual top level's, iT[m][0] is never read
+  std::vector<double> imu(K), ck(K), iT(A * (nL + 1), 0.0);
+  for (size_t k = 0; k < K; ++k) {
+    if (!(mu[k] > 0.0 && mu[k] <= 1.0))
+      return fail("frei_emergent: mu must lie in (0, 1] (angle " + std::to_string(k) + ")");
+    imu[k] = 1.0 / mu[k];
+    if (weights) {
+      if (!std::isfinite(weights[k]))
+        return fail("frei_emergent: weights must be finite (angle " + std::to_string(k) + ")");
+      ck[k] = weights[k] * mu[k];
+    }
+  }
+  for (size_t m = 0; m < A; ++m) {
+    for (size_t l = 1; l < nL; ++l) {
+      const double t = T[m * nL + l];
+      if (!(std::isfinite(t) && t > 0.0))
+        return fail("frei_emergent: T must be finite and positive (atmosphere " +
+                    std::to_string(m) + ", layer " + std::to_string(l) + ")");
+      iT[m * (nL + 1) + l] = 1.0 / t;
+    }
+    iT[m * (nL + 1) + nL] = iT[m * (nL + 1) + nL - 1];
+  }
+  if (!dtaus && !(c->d_dtaus && (c->batch_api ? c->dtaus_batch_valid : c->dtaus_valid)))
+    return fail(c->batch_api
+                    ? "no device dtaus: run frei_run_batch_ex with keep_dtaus first, or pass dtaus"
+                    : "no device dtaus: run frei_run first or pass dtaus");
+  TRY(set_device(c));
+  double *u_dt = nullptr, *d_iT = nullptr, *d_imu = nullptr, *d_ck = nullptr, *d_int = nullptr,
+         *d_flux = nullptr;
+  PostTimer tm;
+  int rc = 0;
+  if (dtaus && !(rc = dalloc(&u_dt, A * per))) rc = h2d(u_dt, dtaus, A * per, c->stream);
+  if (!rc) rc = dalloc(&d_iT, iT.size());
+  if (!rc) rc = dalloc(&d_imu, K);
+  if (!rc && flux) rc = dalloc(&d_ck, K);
+  if (!rc && intensity) rc = dalloc(&d_int, A * K * n);
+  if (!rc && flux) rc = dalloc(&d_flux, A * n);
+  if (!rc) rc = h2d(d_iT, iT.data(), iT.size(), c->stream);
+  if (!rc) rc = h2d(d_imu, imu.data(), K, c->stream);
+  if (!rc && flux) rc = h2d(d_ck, ck.data(), K, c->stream);
+  if (!rc) {
+    tm.begin(c->stream);
+    launch_emergent(u_dt ? u_dt : c->d_dtaus, c->d_c1, c->d_hcl, d_iT, d_imu, d_ck, n_mu, c->nL,
+                    c->nlam, c->n_atm, d_int, d_flux, c->stream);
+    if (hipGetLastError() != hipSuccess) rc = fail("emergent kernel launch failed");
+    tm.end(c->stream);
+  }
+  auto d2h = [&](double* h, const double* d, size_t cnt) {
+    if (!rc && hipMemcpyAsync(h, d, cnt * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
+                   hipSuccess)
+      rc = fail("emergent copy failed");
+  };
+  if (intensity) d2h(intensity, d_int, A * K * n);
+  if (flux) d2h(flux, d_flux, A * n);
+  // the host vectors are read by the uploads until here
+  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("emergent kernel failed");
+  tm.read(c);
+  dfree(u_dt), dfree(d_iT), dfree(d_imu), dfree(d_ck), dfree(d_int), dfree(d_flux);
+  if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
+  return rc;
+}
+
 int frei_post_timing(frei_ctx* c, double* ms) {
   if (!c || !ms) return fail("null argument");
   *ms = c->post_ms;

@@ -17,6 +17,7 @@ from .binning import BinnedTable
 from .chemistry import ChemistryTable, fixed_provider_mmr, provider_mmr
 from .chemistry import chemistry as mock_chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, UM
+from .emergent import emergent_call, pick
 from .opacity import SeparableTable, sigma_scattering, table_values
 from .transit import transit_call
 from .units import scalar, value
@@ -414,6 +415,15 @@ class Engine:
         k + 1: (depth, tau_slant)."""
         depth, tau = transit_call(self, 1, radii, R_star, dtaus, want_tau)
         return (depth[0], tau[0]) if want_tau else depth[0]
+
+    def emergent(self, T, mu=None, weights=None, dtaus=None, want_intensity=False):
+        """Ray-traced emergent flux [n_lam] of this slice's wavelengths (frei_emergent; pure
+        absorption) from the temperatures ``T`` [n_layers] and ``dtaus`` (host array) or, with
+        None, the dtaus the last run left on the device: ``2 pi sum_k weights[k] mu[k] I(mu[k])``
+        over the angles ``mu`` (default :func:`frei_amd.gauss_angles` (4)).  ``want_intensity``
+        also returns the intensities [n_mu][n_lam]: (flux, intensity); ``mu`` without
+        ``weights`` returns the intensities only."""
+        return pick(*emergent_call(self, 1, T, mu, weights, dtaus, want_intensity), m=0)
 
     def path(self):
         """Sweep implementation the tables select: dict(fast, lds_steps, contracted, nan)."""

@@ -309,9 +309,57 @@ int frei_post_batch(frei_ctx* ctx, const double* dtaus, const double* spectra, c
  */
 int frei_transit(frei_ctx* ctx, const double* dtaus, const double* radii, double r_star,
                  double* depth, double* tau_slant);
+/*
+ * Emergent specific intensities I(mu) at the top of every atmosphere of the context at a set of
+ * viewing angles, and their quadrature over the disk: the formal solution along rays through
+ * the final emit's vertical optical depths (K11, one launch over (wavelength block,
+ * atmosphere)).  The reference has no counterpart; this is the definition.
+ * Layer 0 is the bottom.  Levels l = 1 .. nL-1 (nL = n_layers) carry the temperatures
+ * T_l = T[l]; the virtual top level nL has T_nL = T_{nL-1} (emit's rule for its last step).
+ *   Shell l (1 <= l <= nL-1) lies between levels l and l + 1; its vertical optical depth is row
+ *   l of dtaus (emit order, as frei_run returns them).  Row 0 (the ones placeholder) is never
+ *   read; T[0] is never read.
+ *   The dtaus are absorption optical depths (twostream.py:371-373 forms them from k, not from
+ *   k + sigma): this is the pure-absorption formal solution.  Scattering enters neither as
+ *   extinction nor as source.
+ * Per wavelength j, atmosphere m and angle k with 0 < mu[k] <= 1:
+ *   B_l   = c1[j] / expm1((h c / lk[j]) * (1 / T_l))    the context's own Planck constants
+ *                                                       (frei_set_grid)
+ *   I     = B_1                                         opaque base at level 1 (as frei_transit)
+ *   for l = 1 .. nL-1, ascending:
+ *       x  = dtaus[l][j] / mu[k]
+ *       e  = exp(-x);  em = -expm1(-x)
+ *       v  = 1 - em / x    (v(0) = 0, v(inf) = 1)
+ *       u  = em - v
+ *       I  = I * e + (B_l * u + B_{l+1} * v)
+ *   intensity[m][k][j] = I
+ *   flux[m][j] = 2 pi * sum_k c_k * intensity[m][k][j],  c_k = weights[k] * mu[k] formed on the
+ *                host, added in ascending k starting from the k = 0 term
+ * This is the exact integral of a source function linear in tau across each shell (the
+ * two-stream's Bprime makes the same assumption).  e, u and v are non-negative and
+ * e + u + v = 1: every step is a convex combination.  v cancels for small x and is evaluated
+ * there from the series x/2 - x^2/6 + x^3/24 - ...; e is never formed as 1 - em (a hot base
+ * under a cold opaque top would lose the answer), and I * e underflows smoothly.  x = 0 leaves
+ * I unchanged; x = inf gives B_{l+1}.  NaN or inf in a column stays in that column; nothing in
+ * the input columns is checked.
+ * dtaus[n_atm][n_layers][n_lam] is a host array to upload, or NULL for the device copy the last
+ * frei_run / frei_run_batch_ex(keep_dtaus) left ("no device dtaus" when there is none).
+ * T[n_atm][n_layers] is a host array, always given: the temperatures that belong to the kept
+ * dtaus are the caller's business, as the radii are for frei_transit.  mu[n_mu], 1 <= n_mu <= 64;
+ * weights[n_mu] is NULL exactly when flux is NULL.
+ * Outputs intensity[n_atm][n_mu][n_lam] and flux[n_atm][n_lam]; either may be NULL, not both,
+ * and nothing is allocated or written for an absent one.  n_atm = 1 on a context from
+ * frei_ctx_create; a wavelength-slice context gives its own columns.  intensity[m][k] is bitwise
+ * the same whatever else is in the call (other angles, n_mu, with or without flux, single or
+ * batched context).  Errors (return codes; the context stays usable): null T or mu, both
+ * outputs null, weights and flux not both present or both absent, n_mu out of range, a mu that
+ * is not finite, <= 0 or > 1, a non-finite weight, a T[m][l], l >= 1, not finite and positive.
+ */
+int frei_emergent(frei_ctx* ctx, const double* dtaus, const double* T, const double* mu,
+                  const double* weights, int n_mu, double* intensity, double* flux);
 /* HIP-event milliseconds of the kernels of the last frei_milne_pressure, frei_contribution,
- * frei_post_batch or frei_transit call on this context (uploads and read-backs excluded); 0
- * before any. */
+ * frei_post_batch, frei_transit or frei_emergent call on this context (uploads and read-backs
+ * excluded); 0 before any. */
 int frei_post_timing(frei_ctx* ctx, double* ms);
 
 /* Which sweep implementation the context's current tables select (after metadata build):

@@ -14,4 +14,5 @@ done
 /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -ffp-contract=off -fPIC -shared -std=c++17 \
   -Iinclude "$@" frei_amd/csrc/frei_kernels.hip frei_amd/csrc/frei_runtime.hip \
   frei_amd/csrc/frei_binning.hip frei_amd/csrc/frei_stellar.hip frei_amd/csrc/frei_transit.hip \
+  frei_amd/csrc/frei_observe.hip frei_amd/csrc/frei_emergent.hip \
   -o "$OUT" -ldl
