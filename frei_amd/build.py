@@ -6,6 +6,10 @@ hash on its first line, the compiler's identity after it), not by modification t
 copied tree (the GPU box's snapshot) does not preserve meaningfully.  ``frei_amd._native`` checks
 the source hash at load time and refuses a library built from other sources; the compiler line is
 only compared at build time (loading runs no compiler) and named in the load error.
+
+``build()`` also builds tests/csrc/libfrei_mathprobe.so (``build_probe()``: frei_math.h's functions
+one value per lane, for tests/test_gpu_math.py) when its source is present, with the same
+compiler, flags and include paths and a stamp of its own in the same format.
 """
 import glob
 import hashlib
@@ -21,6 +25,10 @@ SOURCES = ["csrc/frei_kernels.hip", "csrc/frei_runtime.hip", "csrc/frei_binning.
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 LIB = os.path.join(HERE, "libfrei_hip.so")
 STAMP = LIB + ".stamp"
+# the test-only probe of frei_math.h (tests/test_gpu_math.py); built when its source is present
+MATH_H = os.path.join(HERE, "csrc", "frei_math.h")
+PROBE_SRC = os.path.join(ROOT, "tests", "csrc", "frei_math_probe.hip")
+PROBE_LIB = os.path.join(ROOT, "tests", "csrc", "libfrei_mathprobe.so")
 
 
 def _hipcc():
@@ -84,7 +92,45 @@ def stamp_matches(lib=LIB):
     return os.path.exists(lib) and digest == source_hash()
 
 
+def probe_hash():
+    """SHA-256 over the probe's source, frei_math.h and the flags, as source_hash()."""
+    h = hashlib.sha256()
+    for f in (PROBE_SRC, MATH_H):
+        h.update(os.path.relpath(f, ROOT).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(FLAGS).encode())
+    return h.hexdigest()
+
+
+def probe_stamp_matches():
+    """True when the probe exists and its stamp carries the hash of the current probe source,
+    frei_math.h and flags (load-time check: runs no compiler)."""
+    return os.path.exists(PROBE_LIB) and read_stamp(PROBE_LIB)[0] == probe_hash()
+
+
+def build_probe(verbose=False):
+    """tests/csrc/libfrei_mathprobe.so: frei_math.h's functions one value at a time
+    (tests/test_gpu_math.py), with the library's compiler, flags and include paths."""
+    if probe_stamp_matches() and read_stamp(PROBE_LIB)[1] == compiler_id().strip():
+        return PROBE_LIB
+    digest = probe_hash()
+    cmd = [_hipcc(), *FLAGS, "-I" + os.path.join(ROOT, "include"),
+           "-I" + os.path.join(HERE, "csrc"), PROBE_SRC, "-o", PROBE_LIB + ".tmp"]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    os.replace(PROBE_LIB + ".tmp", PROBE_LIB)
+    with open(PROBE_LIB + ".stamp.tmp", "w") as f:
+        f.write(digest + "\n" + compiler_id().strip() + "\n")
+    os.replace(PROBE_LIB + ".stamp.tmp", PROBE_LIB + ".stamp")
+    return PROBE_LIB
+
+
 def build(verbose=False):
+    if os.path.exists(PROBE_SRC):
+        build_probe(verbose)
     if stamp_matches() and read_stamp()[1] == compiler_id().strip():
         return LIB
     digest = source_hash()

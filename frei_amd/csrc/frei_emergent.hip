@@ -15,7 +15,7 @@
 // the tiling.  No LDS, no atomics, no barrier.
 //
 // Per (shell, angle) one exponential polynomial gives e = exp(-x), em = 1 - e and v together
-// (exp_em below), so the step costs one exponential and one division, not two exponentials and
+// (exp_em, frei_math.h), so the step costs one exponential and one division, not two exponentials and
 // a division.  Every angle's recurrence is the same operations in the same order whichever
 // instantiation runs it (the library is built with -ffp-contract=off: nothing is fused but the
 // explicit fma of the polynomial and of the division core), so intensity[m][k] is bitwise
@@ -49,55 +49,8 @@ constexpr int kAhead = 4;
 static_assert(kTile >= 1 && kTile <= 8 && kAhead >= 1, "tile of 1 .. 8 angles");
 constexpr double kTwoPi = 6.283185307179586;
 
-// For y <= 0 (or NaN): e = exp(y), em = 1 - e = -expm1(y), and the short-range quantities
-//   n0 = (the reduction took no power of two: |y| <= ln2 / 2), q = (e - 1 - y) / y^2 for n0,
-// from fm::exp_neg's sequence (same constants, same fma order: e is bit-identical to it).  With
-// n0 the reduced argument is y itself and the polynomial is 1 + y (1 + y q), so
-//   em = -y (1 + y q) and (e - 1 - y) / y = y q
-// come without cancellation; otherwise e <= 2^-1/2 and 1 - e loses less than two bits.  e is
-// never formed as 1 - em.  y below -1100 (and -inf) is clamped: e underflows to 0 smoothly.
-__device__ __forceinline__ void exp_em(double y, double& e, double& em, bool& n0, double& q) {
-  y = (y < -1100.0) ? -1100.0 : y;
-  const double n = __builtin_rint(y * fm::c64(0x3ff71547652b82feull));
-  double r = __builtin_fma(fm::c64(0xbfe62e42fefa39efull), n, y);
-  r = __builtin_fma(fm::c64(0xbc7abc9e3b39803full), n, r);
-  double p = __builtin_fma(fm::c64(0x3e5ade156a5dcb37ull), r, fm::c64(0x3e928af3fca7ab0cull));
-  p = fm::hfma(r, p, 0x3ec71dee623fde64ull);
-  p = fm::hfma(r, p, 0x3efa01997c89e6b0ull);
-  p = fm::hfma(r, p, 0x3f2a01a014761f6eull);
-  p = fm::hfma(r, p, 0x3f56c16c1852b7b0ull);
-  p = fm::hfma(r, p, 0x3f81111111122322ull);
-  p = fm::hfma(r, p, 0x3fa55555555502a1ull);
-  p = fm::hfma(r, p, 0x3fc5555555555511ull);
-  q = fm::hfma(r, p, 0x3fe000000000000bull);
-  const double p1 = __builtin_fma(r, q, 1.0);
-  e = __builtin_ldexp(__builtin_fma(r, p1, 1.0), (int)n);
-  n0 = n == 0.0;
-  em = n0 ? -(r * p1) : 1.0 - e;
-}
-
-// B = c1 / expm1(hcl / T) as c1 e / (1 - e) with e = exp(-hcl / T) (the sweeps' planck,
-// frei_kernels.hip), the denominator from exp_em: no cancellation at long wavelengths.
-__device__ __forceinline__ double planck_em(double c1, double hcl, double iT) {
-  double e, em, q;
-  bool n0;
-  exp_em(-(hcl * iT), e, em, n0, q);
-  return fm::div(c1 * e, em);
-}
-
-// One shell along one ray: I = I e + (Bl u + Bn v), x = dtau / mu.
-//   v = 1 - em / x, by x q where the polynomial's q is that quotient's series (x <= ln2 / 2: no
-//   cancellation, v(0) = 0), by the division above it (x >= 2^60, inf included: v = 1 exactly,
-//   as the rounded 1 - em / x is); u = em - v.  e, u, v >= 0 and e + u + v = 1.
-__device__ __forceinline__ void shell_step(double& I, double x, double Bl, double Bn) {
-  double e, em, q;
-  bool n0;
-  exp_em(-x, e, em, n0, q);
-  const double xd = __builtin_fmin(x, 0x1p60);
-  const double v = n0 ? x * q : 1.0 - fm::div(em, xd);
-  const double u = em - v;
-  I = I * e + (Bl * u + Bn * v);
-}
+// exp_em, planck_em and shell_step (one exponential polynomial per shell and angle) are in
+// frei_math.h with the primitives they are built on.
 
 // The angles k0 .. k0 + TI - 1 of one column: the walk from level 1 to the top.  col: the
 // column's row 0; it[l] = 1 / T_l for l = 1 .. nS + 1 (the virtual top level repeats the last).

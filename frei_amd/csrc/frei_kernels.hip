@@ -74,23 +74,7 @@ __device__ long long g_ptrace[2 * 8 * 16 * (kPtPh + 1) * 2];
 #endif
 
 // ---------------------------------------------------------------- device math
-// twostream.py:64-67: 2hc^2/lam^5 / expm1(hc / (lam k T)).  The exponent is formed as
-// (hc / (lam k)) * (1 / T) — a per-wavelength constant (host) times a per-layer one (the step
-// record) — instead of one division per update: within 1.5 ulp of the reference's
-// hc / ((lam k) T), which moves spectra and T by < 1e-13.
-//
-// The value is formed as c1 e / (1 - e) with e = exp(-x), from the transmission's exp (its
-// coefficients are wave-uniform SGPR constants the sweep already holds) instead of an expm1
-// whose ten coefficients occupied 20 VGPRs per lane: four VALU and 20 VGPRs fewer per update,
-// no range guard (e in [0, 1]: the quotient never overflows, and e underflows to the
-// reference's 0 at x > 745).  Error: a few ulp, growing as ~1 ulp / x for x < 1 (the
-// cancellation in 1 - e) — 1e-15 relative at x = 0.1, far inside the 1e-10 parity bar.  A NaN
-// temperature propagates.  Between x = 709.8 (where numpy's expm1 overflows, B = 0) and 745 it
-// returns the subnormal c1 e instead of 0.
-__device__ __forceinline__ double planck(double c1, double hcl, double iT) {
-  const double e = fm::exp_neg_unclamped(-(hcl * iT));
-  return fm::div(c1 * e, 1.0 - e);
-}
+// planck(c1, hcl, iT), twostream.py:64-67, is in frei_math.h with the primitives it is built on.
 
 // twostream.py:97-177 with g_0 = 0 (call sites 389, 518), E() of :70-94.
 __device__ __forceinline__ void two_stream(double w0, double dtau, double B1, double B2,

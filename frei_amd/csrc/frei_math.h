@@ -1,5 +1,8 @@
-// frei_math.h — fp64 exp / expm1 / sqrt / division for the sweep kernels, bit-identical to
-// the ocml / LLVM lowering they replace but cheaper on gfx950's VALU.
+// frei_math.h — fp64 exp / sqrt / division / reciprocal for the sweep kernels, cheaper on
+// gfx950's VALU than the ocml / LLVM lowering they replace, and the small formulas built on them
+// (planck, exp_em, planck_em, shell_step).  What each function guarantees is checked against
+// exact arithmetic on the GPU by tests/test_gpu_math.py (through tests/csrc/frei_math_probe.hip);
+// the figures quoted here are that test's, measured on MI355X.
 //
 // Why: the sweep is fp64-VALU-bound, and three lowering choices cost ~25% of
 // its instructions per flux update:
@@ -7,24 +10,35 @@
 //     polynomial coefficient is first copied into a VGPR pair (two v_mov_b32 per term, ~18
 //     VALU moves per call).  Here each term of the sweep's exp (exp_neg*) is one
 //     `v_fma_f64 p, r, p, s[c_k]` with the coefficient in an SGPR pair (materialised by SALU
-//     moves, off the VALU port).
+//     moves, off the VALU port).  Same constants, same fma order: bit-identical to the
+//     compiler's ::exp for every x <= 0 (2^20 uniform points, every reduction boundary, the
+//     subnormal-result window), within 0.80 ulp of exp(x).
 //   * IEEE fp64 division is lowered with v_div_scale x2 / v_div_fmas / v_div_fixup around the
 //     Newton-Raphson core.  Those only act when an operand is within ~2^768 of the exponent
-//     range ends or denormal; every quotient the sweep forms (optical depths, Planck terms,
-//     albedos, 1/chi) is far from them, so the bare core below returns the same bits.
+//     range ends, denormal, zero, infinite or NaN; every quotient the sweep forms (optical
+//     depths, Planck terms, albedos, 1/chi) is far from the range ends, so the bare core below
+//     serves.  Of the special operands only a zero numerator is kept exact (+-0 / b has the IEEE
+//     sign); a zero, infinite or NaN divisor gives NaN.
 //   * sqrt's denormal-range scaling (x < 2^-767) is likewise dropped: the sweep takes square
 //     roots of 1 - w0 style quantities in (2^-53, 2].
 //   * division and sqrt refine the hardware estimate with one Newton-Raphson step fewer than
-//     the LLVM / ocml sequences: gfx950's v_rcp_f64 and
-//     v_rsq_f64 are good to ~2^-24 and one step brings the reciprocal to <= 11 ulp
-//     (tools/rcp_acc.hip), after which the quotient's residual correction (sqrt: the final
-//     Newton correction) still rounds correctly — 0 differences from the IEEE result in 2^28
-//     random operands per range (tools/mathcheck.hip).  Not a proof: a result within ~2^-45
-//     ulp of a rounding midpoint could come out one ulp off (probability ~2^-44 per call).
+//     the LLVM / ocml sequences (gfx950's v_rcp_f64 and v_rsq_f64 are good to ~2^-24), after
+//     which the quotient's residual correction (sqrt: the final Newton correction) still
+//     rounds correctly on every operand that is not constructed to defeat it: 0 differences
+//     from the correctly rounded result on 2^20 random operands per range and on the operand
+//     families the kernels form ((B1 - B2) / dtau, Emw / E, pi (1 - w0) / Emw, c1 e / (1 - e),
+//     power-of-two divisors).  The results are faithfully rounded, not always correctly
+//     rounded: the shorter refinement leaves the reciprocal (and with it the correction term)
+//     a few ulp off, so a result very close to a rounding midpoint can come out one ulp off.
+//     On 25 000 constructed quotients within 2^-53 ulp of a midpoint, 2762 are the other
+//     neighbour (e.g. 0x1.60cb52fd9f943p+52 / 0x1.ffca01812618bp+52 gives 0x1.60f08b52d22cbp-1,
+//     correctly rounded 0x1.60f08b52d22ccp-1); on 326 constructed arguments whose root is within
+//     2^-45 ulp of a midpoint, 5 are (e.g. sqrt(0x1.d539343604b1cp-1) gives
+//     0x1.ea2531e60718fp-1, correctly rounded 0x1.ea2531e607190p-1); none is further off.
+//     No bitwise identity between sweep forms depends on correct rounding: every form calls
+//     the same div and sqrt.
 //     -1.2 % sweep time at 500k, -3.9 % at 62.5k (profiles/r02_ab_short_div.txt).
-// Otherwise every function keeps the exact operation sequence of the lowering it replaces
-// (same constants, same fma order), so results are identical wherever the dropped guards
-// would not fire; tools/mathcheck.hip checks that on the GPU over random and edge-case inputs.
+// tools/mathcheck.hip is the stand-alone 2^28-operand version of the bitwise comparisons.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -136,14 +150,17 @@ __device__ __forceinline__ double rcp_nr(double b) {
 }
 
 // a / b: LLVM's fp64 division core (rcp, one Newton-Raphson step where LLVM takes two,
-// quotient, one residual correction) without the div_scale / div_fmas / div_fixup guards.
+// quotient, one residual correction) without the div_scale / div_fmas / div_fixup guards; the
+// sign of the quotient estimate is copied onto the result (one v_bfi_b32: a zero numerator of
+// either sign gives the IEEE zero; no change for any other operand; no measurable cost at 500k).
 __device__ __forceinline__ double div(double a, double b) {
   double r = __builtin_amdgcn_rcp(b);
   const double e = __builtin_fma(-b, r, 1.0);
   r = __builtin_fma(r, e, r);
   const double q = a * r;
   const double rem = __builtin_fma(-b, q, a);
-  return __builtin_fma(rem, r, q);
+  // q has the quotient's sign; for a = -0 and b > 0 the sum below is (+0) + (-0) = +0
+  return __builtin_copysign(__builtin_fma(rem, r, q), q);
 }
 
 // sqrt(x): ocml's rsq + Newton-Raphson sequence (its last correction dropped) without the
@@ -177,4 +194,78 @@ __device__ __forceinline__ double sqrt_pos(double x) {
 }
 
 }  // namespace fm
+
+// ---------------------------------------------------------------- formulas on the primitives
+// The sweeps' Planck function (frei_kernels.hip) and the emergent rays' exponential forms
+// (frei_emergent.hip) live here so that tests/csrc/frei_math_probe.hip can call them one value at
+// a time; the kernels' code is unchanged by where they are declared.
+
+// twostream.py:64-67: 2hc^2/lam^5 / expm1(hc / (lam k T)).  The exponent is formed as
+// (hc / (lam k)) * (1 / T) — a per-wavelength constant (host) times a per-layer one (the step
+// record) — instead of one division per update: within 1.5 ulp of the reference's
+// hc / ((lam k) T), which moves spectra and T by < 1e-13.
+//
+// The value is formed as c1 e / (1 - e) with e = exp(-x), from the transmission's exp (its
+// coefficients are wave-uniform SGPR constants the sweep already holds) instead of an expm1
+// whose ten coefficients occupied 20 VGPRs per lane: four VALU and 20 VGPRs fewer per update,
+// no range guard (e in [0, 1]: the quotient never overflows, and e underflows to the
+// reference's 0 at x > 745).  Error: a few ulp, growing as ~1 ulp / x for x < 1 (the
+// cancellation in 1 - e) — 1e-15 relative at x = 0.1, far inside the 1e-10 parity bar.  A NaN
+// temperature propagates.  Between x = 709.8 (where numpy's expm1 overflows, B = 0) and 745 it
+// returns the subnormal c1 e instead of 0.
+__device__ __forceinline__ double planck(double c1, double hcl, double iT) {
+  const double e = fm::exp_neg_unclamped(-(hcl * iT));
+  return fm::div(c1 * e, 1.0 - e);
+}
+
+// For y <= 0 (or NaN): e = exp(y), em = 1 - e = -expm1(y), and the short-range quantities
+//   n0 = (the reduction took no power of two: |y| <= ln2 / 2), q = (e - 1 - y) / y^2 for n0,
+// from fm::exp_neg's sequence (same constants, same fma order: e is bit-identical to it).  With
+// n0 the reduced argument is y itself and the polynomial is 1 + y (1 + y q), so
+//   em = -y (1 + y q) and (e - 1 - y) / y = y q
+// come without cancellation; otherwise e <= 2^-1/2 and 1 - e loses less than two bits.  e is
+// never formed as 1 - em.  y below -1100 (and -inf) is clamped: e underflows to 0 smoothly.
+__device__ __forceinline__ void exp_em(double y, double& e, double& em, bool& n0, double& q) {
+  y = (y < -1100.0) ? -1100.0 : y;
+  const double n = __builtin_rint(y * fm::c64(0x3ff71547652b82feull));
+  double r = __builtin_fma(fm::c64(0xbfe62e42fefa39efull), n, y);
+  r = __builtin_fma(fm::c64(0xbc7abc9e3b39803full), n, r);
+  double p = __builtin_fma(fm::c64(0x3e5ade156a5dcb37ull), r, fm::c64(0x3e928af3fca7ab0cull));
+  p = fm::hfma(r, p, 0x3ec71dee623fde64ull);
+  p = fm::hfma(r, p, 0x3efa01997c89e6b0ull);
+  p = fm::hfma(r, p, 0x3f2a01a014761f6eull);
+  p = fm::hfma(r, p, 0x3f56c16c1852b7b0ull);
+  p = fm::hfma(r, p, 0x3f81111111122322ull);
+  p = fm::hfma(r, p, 0x3fa55555555502a1ull);
+  p = fm::hfma(r, p, 0x3fc5555555555511ull);
+  q = fm::hfma(r, p, 0x3fe000000000000bull);
+  const double p1 = __builtin_fma(r, q, 1.0);
+  e = __builtin_ldexp(__builtin_fma(r, p1, 1.0), (int)n);
+  n0 = n == 0.0;
+  em = n0 ? -(r * p1) : 1.0 - e;
+}
+
+// B = c1 / expm1(hcl / T) as c1 e / (1 - e) with e = exp(-hcl / T) (the sweeps' planck above),
+// the denominator from exp_em: no cancellation at long wavelengths.
+__device__ __forceinline__ double planck_em(double c1, double hcl, double iT) {
+  double e, em, q;
+  bool n0;
+  exp_em(-(hcl * iT), e, em, n0, q);
+  return fm::div(c1 * e, em);
+}
+
+// One shell along one ray: I = I e + (Bl u + Bn v), x = dtau / mu.
+//   v = 1 - em / x, by x q where the polynomial's q is that quotient's series (x <= ln2 / 2: no
+//   cancellation, v(0) = 0), by the division above it (x >= 2^60, inf included: v = 1 exactly,
+//   as the rounded 1 - em / x is); u = em - v.  e, u, v >= 0 and e + u + v = 1.
+__device__ __forceinline__ void shell_step(double& I, double x, double Bl, double Bn) {
+  double e, em, q;
+  bool n0;
+  exp_em(-x, e, em, n0, q);
+  const double xd = __builtin_fmin(x, 0x1p60);
+  const double v = n0 ? x * q : 1.0 - fm::div(em, xd);
+  const double u = em - v;
+  I = I * e + (Bl * u + Bn * v);
+}
+
 }  // namespace frei

@@ -98,6 +98,53 @@ def test_build_script_lists_every_hip_source():
     assert sorted(os.path.basename(s) for s in build.SOURCES) == hips
 
 
+def test_math_probe_and_tools_compile_against_the_current_math_header():
+    """Everything outside the library that includes frei_math.h — the test-only probe
+    (tests/csrc/frei_math_probe.hip) and the stand-alone tools — still parses against it with the
+    library's flags (hipcc -fsyntax-only): a function removed from the header must not leave a
+    checker behind that no longer builds.  Skipped only without a compiler."""
+    import glob
+    import shutil
+    import subprocess
+    from frei_amd import build
+    hipcc = build._hipcc()
+    if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+        pytest.skip("no hipcc")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(build.__file__)))
+    users = [build.PROBE_SRC]
+    for path in sorted(glob.glob(os.path.join(root, "tools", "*.hip"))):
+        with open(path) as f:
+            if '#include "frei_math.h"' in f.read():
+                users.append(path)
+    assert os.path.exists(build.PROBE_SRC) and len(users) >= 2, users
+    flags = [f for f in build.FLAGS if f != "-shared"]
+    procs = [(path, subprocess.Popen(
+        [hipcc, *flags, "-fsyntax-only", "-I" + os.path.join(root, "include"),
+         "-I" + os.path.join(root, "frei_amd", "csrc"), path],
+        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)) for path in users]
+    for path, p in procs:
+        out, _ = p.communicate(timeout=300)
+        assert p.returncode == 0, f"{os.path.relpath(path, root)} does not compile:\n{out[-3000:]}"
+
+
+def test_math_probe_stamp_follows_the_header_and_the_flags(tmp_path, monkeypatch):
+    """build.probe_hash() covers the probe source, frei_math.h and the flags, so a probe built
+    from another header or with other flags is refused by tests/test_gpu_math.py."""
+    from frei_amd import build
+    h0 = build.probe_hash()
+    monkeypatch.setattr(build, "FLAGS", [*build.FLAGS, "-DX"])
+    assert build.probe_hash() != h0
+    monkeypatch.undo()
+    copy = tmp_path / "frei_math.h"
+    with open(build.MATH_H, "rb") as f:
+        copy.write_bytes(f.read() + b"\n")
+    monkeypatch.setattr(build, "MATH_H", str(copy))
+    assert build.probe_hash() != h0
+    monkeypatch.undo()
+    assert build.probe_hash() == h0
+    assert "-ffp-contract=off" in build.FLAGS and "--offload-arch=gfx950" in build.FLAGS
+
+
 def test_chemistry_table_interpolation_contract():
     """The ChemistryTable interface (engine: frei_set_chemistry; checker:
     oracle.ChemistryTable): exact at nodes, linear in T and log10 p between them, clamped
