@@ -11,6 +11,7 @@ from .chemistry import ChemistryTable, chemistry, iso_to_mass, iso_to_species
 from .core import (B_star, F_TOA, Grid, Planet, Spectrum, contribution_function,
                    effective_temperature,
                    effective_temperature_milne, effective_temperature_planck, wavelength_grid)
+from .crosscorr import CrossCorrelation, CrossCorrelator, kp_vsys_map
 from .emergent import gauss_angles
 from .engine import Engine, balanced_edges, partition, trapz_weights
 from .observe import Instrument
@@ -31,4 +32,5 @@ __all__ = ["Planet", "Grid", "Spectrum", "effective_temperature", "wavelength_gr
            "BinnedTable", "open_cross_section", "contribution_function", "BatchEngine",
            "batched_emission_spectra", "ChemistryTable", "BatchRecord", "BatchResult",
            "StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum",
-           "level_radii", "Instrument", "gauss_angles"]
+           "level_radii", "Instrument", "gauss_angles", "CrossCorrelator", "CrossCorrelation",
+           "kp_vsys_map"]

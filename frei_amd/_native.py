@@ -117,6 +117,13 @@ SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_int32), _dp, _dp, _dp,
                                       ctypes.c_int, _dp, _dp, _ip, _dp]),
     "frei_obs_destroy": (ctypes.c_int, [_vp]),
+    "frei_ccf_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _i64, _i64,
+                                       ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _dp,
+                                       ctypes.c_int, _dp, _dp]),
+    "frei_ccf_apply": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, _dp, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_int32), _dp, _dp, ctypes.c_int,
+                                      _dp, _dp, _dp, _ip, _dp]),
+    "frei_ccf_destroy": (ctypes.c_int, [_vp]),
 }
 
 _lib = None

@@ -399,6 +399,26 @@ class BatchResult(list):
                        engine=None if kind == "transit" else self.engine, weighting=weighting,
                        data=data, sigma=sigma, R_p=R_p, R_star=R_star)
 
+    def cross_correlate(self, cc, kind="eclipse", depth=None, R_p=None, R_star=None,
+                        offset=None):
+        """Every atmosphere against high-resolution data over a grid of trial velocities
+        (``cc``: :class:`~frei_amd.crosscorr.CrossCorrelator`, K12) ->
+        :class:`~frei_amd.crosscorr.CrossCorrelation`.  ``kind``: "flux" takes the emergent
+        spectra as templates, "eclipse" the planet-to-star flux ratio F_p / F_star
+        (R_p / R_star)^2 — both read the spectra where the run left them on the device — and
+        "transit" minus ``depth`` [n_atm][n_lam] (default: :meth:`transmission` with these
+        radii).  Stars and radii as in :meth:`observe`; ``offset`` (a number per atmosphere) is
+        subtracted from each template."""
+        from .crosscorr import cross_correlate
+        A = len(self)
+        planets = self.planets if self.planets is not None else [None] * A
+        x = None
+        if kind == "transit":
+            x = self.transmission(R_p=R_p, R_star=R_star) if depth is None else depth
+        return cross_correlate(cc, kind, planets, self.engine.lam_um, x=x,
+                               engine=None if kind == "transit" else self.engine, R_p=R_p,
+                               R_star=R_star, offset=offset)
+
     def close(self):
         self.engine.close()
 

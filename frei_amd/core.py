@@ -242,6 +242,18 @@ class Grid:
                        x=np.asarray(getattr(spectrum, "flux", spectrum), dtype=float),
                        data=data, sigma=sigma, R_p=R_p, R_star=R_star)
 
+    def cross_correlate(self, cc, spectrum, kind="eclipse", R_p=None, R_star=None, offset=None):
+        """``spectrum`` (the :class:`Spectrum` of emission_spectrum or transmission_spectrum)
+        against high-resolution data over a grid of trial velocities (``cc``:
+        :class:`~frei_amd.crosscorr.CrossCorrelator`, K12) ->
+        :class:`~frei_amd.crosscorr.CrossCorrelation`.  ``kind``: "flux" the spectrum as it is,
+        "eclipse" F_p / F_star (R_p / R_star)^2, "transit" minus the transit depth.  Star and
+        radii as in :meth:`observe`."""
+        from .crosscorr import cross_correlate
+        return cross_correlate(cc, kind, [self.planet], self.lam,
+                               x=np.asarray(getattr(spectrum, "flux", spectrum), dtype=float),
+                               R_p=R_p, R_star=R_star, offset=offset)
+
     def emission_dashboard(self, *args, **kwargs):
         raise NotImplementedError("plotting is out of scope for the MI355X engine (SURVEY.md §2)")
 

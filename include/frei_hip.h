@@ -550,6 +550,67 @@ int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const
                    int* form_used, double* kernel_ms);
 int frei_obs_destroy(frei_obs* o);
 
+/*
+ * Doppler cross-correlation (K12): batched templates against high-resolution data over a grid
+ * of trial velocities.  The reference has no counterpart; this is the definition.
+ * A correlator holds, resident on `device` with the handle: a native axis of n_lam >= 2 points,
+ * n_pix >= 1 data pixels, n_vel >= 1 trial velocities, n_exp >= 1 exposures; the plan
+ * idx[n_vel][n_pix] (0 <= idx <= n_lam - 2) and frac[n_vel][n_pix] (finite, in [0, 1]): the
+ * native bracket and the weight of its upper point at which pixel p samples a template shifted
+ * by velocity v; the weighted data a[n_exp][n_pix] (finite, any sign) and the pixel weights
+ * w[n_pix] (finite, >= 0, sum > 0).  frei_ccf_create checks all of it on the host before it
+ * touches a device and names the first offending index.
+ */
+typedef struct frei_ccf frei_ccf;
+int frei_ccf_create(frei_ccf** out, int device, int64_t n_lam, int64_t n_pix, int n_vel,
+                    const int32_t* idx, const double* frac, int n_exp, const double* a,
+                    const double* w);
+/*
+ * Template pre-pass, once per call over [n_atm][n_lam]:
+ *   y[m][j] = scale_m * (x[m][j] / den[select_m][j]) - offset_m
+ * den[n_lib][n_lam] with select[n_atm] (NULL: row 0 for all; ignored without den), scale[n_atm]
+ * and offset[n_atm] are each optional; an absent one drops its operation (it is not replaced
+ * by a multiplication by 1 or a subtraction of 0).  x is a host array [n_atm][n_lam] (uploaded
+ * for the call), or NULL with a context: the source is then the emergent row F_up[n_layers - 1]
+ * of every atmosphere, in place in the flux state, under the rules of frei_obs_apply (n_atm ==
+ * the context's atmosphere count, n_lam == its n_lam, the same device; a context of a
+ * wavelength slice does not fit: a pixel's bracket may straddle slices).
+ * Sums: for atmosphere m, velocity v, pixel p, with j = idx[v][p] and t = frac[v][p],
+ *   g = y[m][j] + t * (y[m][j+1] - y[m][j])            (three operations, never contracted)
+ *   S_fg[m][e][v] = sum_p a[e][p] * g
+ *   S_g[m][v]     = sum_p w[p] * g
+ *   S_gg[m][v]    = sum_p (w[p] * g) * g
+ * Order: the pixels are taken in chunks of 4096 and the chunk sums are added in ascending chunk
+ * order; every term enters by one fused multiply-add (a * g, w * g, and (w * g) rounded then
+ * times g).  Within a chunk starting at p0,
+ *   form 1 (VALU): lane l of 64 accumulates the pixels p0 + l, p0 + l + 64, ... in order and
+ *     the 64 lane sums combine in the xor butterfly 32, 16, ..., 1;
+ *   form 2 (fp64 MFMA, v_mfma_f64_16x16x4_f64): the chunk goes in groups of 16 pixels; step s
+ *     = 0 .. 3 of the group at q adds the pixels q + s, q + 4 + s, q + 8 + s, q + 12 + s to S_fg
+ *     in the matrix unit (A = 16 velocities x 4 pixels of g, B = 4 pixels x 16 exposures of a),
+ *     groups and steps ascending, the last group padded with g = 0, a = 0; S_g and S_gg
+ *     accumulate beside it on the VALU, lane k of 4 taking the pixels q + 4 k + s, s = 0 .. 3, of
+ *     every group in order, combined as (k0 + k1) + (k2 + k3).
+ * For a given form the order depends on n_pix alone and there are no atomics: every result is
+ * bitwise the same from call to call, row m of a batched call is bitwise the call on that row
+ * alone, an output is bitwise unchanged when other exposures or velocities are added to or
+ * removed from the handle, and when other outputs are or are not asked for.  A NaN or inf in y
+ * reaches exactly the outputs whose pixels touch it (with t = 0, 0 * NaN also touches); nothing
+ * in x or den is checked.
+ * form: 0 automatic (form 2 from 9 exposures, form 1 below: the measured crossover), 1 or 2 as
+ * above; *form_used receives the form that ran.
+ * Outputs sfg[n_atm][n_exp][n_vel], sg[n_atm][n_vel], sgg[n_atm][n_vel]: any may be NULL, not all
+ * three; nothing is computed or allocated for an absent one.  *form_used and *kernel_ms (HIP
+ * events around the kernels only) may be NULL.  Errors (handle and context stay usable): null
+ * handle, all outputs null, x and ctx both null, a select entry outside [0, n_lib), a context
+ * of another shape or device.
+ */
+int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const double* den,
+                   int n_lib, const int32_t* select, const double* scale, const double* offset,
+                   int form, double* sfg, double* sg, double* sgg, int* form_used,
+                   double* kernel_ms);
+int frei_ccf_destroy(frei_ccf* c);
+
 #ifdef __cplusplus
 }
 #endif
