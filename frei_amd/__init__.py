@@ -12,6 +12,7 @@ from .core import (B_star, F_TOA, Grid, Planet, Spectrum, contribution_function,
                    effective_temperature,
                    effective_temperature_milne, effective_temperature_planck, wavelength_grid)
 from .crosscorr import CrossCorrelation, CrossCorrelator, kp_vsys_map
+from .broaden import BroadenedSpectra, Broadening, BroadeningKernel
 from .emergent import gauss_angles
 from .engine import Engine, balanced_edges, partition, trapz_weights
 from .observe import Instrument

@@ -124,6 +124,20 @@ SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_int32), _dp, _dp, ctypes.c_int,
                                       _dp, _dp, _dp, _ip, _dp]),
     "frei_ccf_destroy": (ctypes.c_int, [_vp]),
+    "frei_brd_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _i64, _dp, _dp,
+                                       ctypes.POINTER(ctypes.c_int32),
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.c_int,
+                                       ctypes.c_double, ctypes.c_double, _dp]),
+    "frei_brd_norm": (ctypes.c_int, [_vp, _dp]),
+    "frei_brd_apply": (ctypes.c_int, [_vp, _vp, _dp, ctypes.c_int, ctypes.c_int, _dp,
+                                      ctypes.c_int, _ip, _dp]),
+    "frei_brd_destroy": (ctypes.c_int, [_vp]),
+    "frei_ccf_apply_brd": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int32), _dp, _dp,
+                                          ctypes.c_int, _dp, _dp, _dp, _ip, _dp]),
+    "frei_obs_apply_brd": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int32), _dp, _dp, _dp,
+                                          ctypes.c_int, _dp, _dp, _ip, _dp]),
 }
 
 _lib = None

@@ -379,7 +379,7 @@ class BatchResult(list):
         return self.engine.emergent(T, mu=mu, weights=weights, want_intensity=want_intensity)
 
     def observe(self, instrument, kind="eclipse", depth=None, weighting=None, data=None,
-                sigma=None, R_p=None, R_star=None):
+                sigma=None, R_p=None, R_star=None, broadening=None):
         """Every atmosphere through ``instrument`` (:class:`~frei_amd.observe.Instrument`, K10)
         -> obs [n_atm][K], or (obs, chi2 [n_atm]) with ``data`` and ``sigma`` [K].  ``kind``:
         "flux" the channel means of the emergent flux, "eclipse" the secondary-eclipse depths
@@ -388,7 +388,9 @@ class BatchResult(list):
         depths of ``depth`` [n_atm][n_lam] (default: :meth:`transmission` with these radii),
         ``weighting`` "stellar" (the default with Planets) or "flat".  Stars are the Planets':
         ``stellar_spectrum``, else ``pi * B_star(T_star)``, distinct ones uploaded once; the radii
-        (cm or Quantities, scalars or one per atmosphere) default to each Planet's."""
+        (cm or Quantities, scalars or one per atmosphere) default to each Planet's.
+        ``broadening`` (:class:`~frei_amd.broaden.Broadening`, K13) broadens the spectra on the
+        device first."""
         from .observe import observe
         A = len(self)
         planets = self.planets if self.planets is not None else [None] * A
@@ -397,10 +399,10 @@ class BatchResult(list):
             x = self.transmission(R_p=R_p, R_star=R_star) if depth is None else depth
         return observe(instrument, kind, planets, self.engine.lam_um, x=x,
                        engine=None if kind == "transit" else self.engine, weighting=weighting,
-                       data=data, sigma=sigma, R_p=R_p, R_star=R_star)
+                       data=data, sigma=sigma, R_p=R_p, R_star=R_star, broadening=broadening)
 
     def cross_correlate(self, cc, kind="eclipse", depth=None, R_p=None, R_star=None,
-                        offset=None):
+                        offset=None, broadening=None):
         """Every atmosphere against high-resolution data over a grid of trial velocities
         (``cc``: :class:`~frei_amd.crosscorr.CrossCorrelator`, K12) ->
         :class:`~frei_amd.crosscorr.CrossCorrelation`.  ``kind``: "flux" takes the emergent
@@ -408,7 +410,9 @@ class BatchResult(list):
         (R_p / R_star)^2 — both read the spectra where the run left them on the device — and
         "transit" minus ``depth`` [n_atm][n_lam] (default: :meth:`transmission` with these
         radii).  Stars and radii as in :meth:`observe`; ``offset`` (a number per atmosphere) is
-        subtracted from each template."""
+        subtracted from each template.  ``broadening``
+        (:class:`~frei_amd.broaden.Broadening`, K13) broadens the spectra (for "transit" minus
+        the depth) on the device first: resident to resident, then the pre-pass."""
         from .crosscorr import cross_correlate
         A = len(self)
         planets = self.planets if self.planets is not None else [None] * A
@@ -417,7 +421,7 @@ class BatchResult(list):
             x = self.transmission(R_p=R_p, R_star=R_star) if depth is None else depth
         return cross_correlate(cc, kind, planets, self.engine.lam_um, x=x,
                                engine=None if kind == "transit" else self.engine, R_p=R_p,
-                               R_star=R_star, offset=offset)
+                               R_star=R_star, offset=offset, broadening=broadening)
 
     def close(self):
         self.engine.close()

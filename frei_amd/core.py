@@ -230,29 +230,33 @@ class Grid:
         return (spec, inten) if want_intensity else spec
 
     def observe(self, instrument, spectrum, kind="eclipse", data=None, sigma=None, R_p=None,
-                R_star=None):
+                R_star=None, broadening=None):
         """``spectrum`` (the :class:`Spectrum` of emission_spectrum or transmission_spectrum)
         through ``instrument`` (:class:`~frei_amd.observe.Instrument`, K10) -> obs [K], or
         (obs, chi2) with ``data`` and ``sigma`` [K].  ``kind``: "flux" the channel means,
         "eclipse" (band integral of F_p / band integral of F_star) (R_p / R_star)^2, "transit"
         the band-averaged transit depth weighted by the stellar flux.  The star is the Planet's
-        ``stellar_spectrum``, else ``pi * B_star(T_star)``; the radii default to the Planet's."""
+        ``stellar_spectrum``, else ``pi * B_star(T_star)``; the radii default to the Planet's.
+        ``broadening`` (:class:`~frei_amd.broaden.Broadening`, K13) broadens the spectrum on the
+        device first."""
         from .observe import observe
         return observe(instrument, kind, [self.planet], self.lam,
                        x=np.asarray(getattr(spectrum, "flux", spectrum), dtype=float),
-                       data=data, sigma=sigma, R_p=R_p, R_star=R_star)
+                       data=data, sigma=sigma, R_p=R_p, R_star=R_star, broadening=broadening)
 
-    def cross_correlate(self, cc, spectrum, kind="eclipse", R_p=None, R_star=None, offset=None):
+    def cross_correlate(self, cc, spectrum, kind="eclipse", R_p=None, R_star=None, offset=None,
+                        broadening=None):
         """``spectrum`` (the :class:`Spectrum` of emission_spectrum or transmission_spectrum)
         against high-resolution data over a grid of trial velocities (``cc``:
         :class:`~frei_amd.crosscorr.CrossCorrelator`, K12) ->
         :class:`~frei_amd.crosscorr.CrossCorrelation`.  ``kind``: "flux" the spectrum as it is,
         "eclipse" F_p / F_star (R_p / R_star)^2, "transit" minus the transit depth.  Star and
-        radii as in :meth:`observe`."""
+        radii as in :meth:`observe`; ``broadening`` broadens the spectrum (for "transit" minus
+        the depth) on the device first."""
         from .crosscorr import cross_correlate
         return cross_correlate(cc, kind, [self.planet], self.lam,
                                x=np.asarray(getattr(spectrum, "flux", spectrum), dtype=float),
-                               R_p=R_p, R_star=R_star, offset=offset)
+                               R_p=R_p, R_star=R_star, offset=offset, broadening=broadening)
 
     def emission_dashboard(self, *args, **kwargs):
         raise NotImplementedError("plotting is out of scope for the MI355X engine (SURVEY.md §2)")

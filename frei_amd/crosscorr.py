@@ -189,14 +189,19 @@ class CrossCorrelator:
         [n_atm] the row of each atmosphere (default row 0), ``scale`` and ``offset`` optional
         numbers per atmosphere; an absent one drops its operation.  ``x=None`` with ``engine=``
         (an Engine or BatchEngine on the whole axis) takes the emergent spectra resident in the
-        engine's flux state.  ``form`` 0 picks the kernel, a member of ``FORMS`` forces it
-        (``form_used`` records the choice).  ``want`` names the sums to compute (``"sfg"``,
-        ``"sg"``, ``"sgg"``; the others are None and cost nothing)."""
+        engine's flux state; a :class:`~frei_amd.broaden.BroadenedSpectra` as ``x`` takes what
+        ``Broadening.apply(keep=True)`` left on the device.  ``form`` 0 picks the kernel, a
+        member of ``FORMS`` forces it (``form_used`` records the choice).  ``want`` names the
+        sums to compute (``"sfg"``, ``"sg"``, ``"sgg"``; the others are None and cost
+        nothing)."""
         want = (want,) if isinstance(want, str) else tuple(want)
         if any(k not in _SUMS for k in want):
             raise ValueError(f"want holds names other than {_SUMS}: {want}")
-        ctx = None
-        if x is None:
+        ctx, brd = None, None
+        if hasattr(x, "owner") and hasattr(x, "serial"):
+            # a BroadenedSpectra (K13): the spectra lie on the device with its Broadening
+            brd, n_atm, single, x = x.handle(), x.n_atm, x.single, None
+        elif x is None:
             if engine is None:
                 raise ValueError("pass x, or engine= for its resident spectra")
             if engine.n_lam != engine.lam_um.size:
@@ -235,11 +240,13 @@ class CrossCorrelator:
                    sg=np.empty((n_atm, V)) if "sg" in want else None,
                    sgg=np.empty((n_atm, V)) if "sgg" in want else None)
         used, ms = ctypes.c_int(0), ctypes.c_double(0.0)
-        N.check(N.lib().frei_ccf_apply(
-            self.handle(), ctx, N.dptr(x), n_atm, N.dptr(den), n_lib,
-            None if sel is None else sel.ctypes.data_as(_i32p), N.dptr(sc), N.dptr(off),
-            int(form), N.dptr(out["sfg"]), N.dptr(out["sg"]), N.dptr(out["sgg"]),
-            ctypes.byref(used), ctypes.byref(ms)))
+        tail = (N.dptr(den), n_lib, None if sel is None else sel.ctypes.data_as(_i32p),
+                N.dptr(sc), N.dptr(off), int(form), N.dptr(out["sfg"]), N.dptr(out["sg"]),
+                N.dptr(out["sgg"]), ctypes.byref(used), ctypes.byref(ms))
+        if brd is not None:
+            N.check(N.lib().frei_ccf_apply_brd(self.handle(), brd, n_atm, *tail))
+        else:
+            N.check(N.lib().frei_ccf_apply(self.handle(), ctx, N.dptr(x), n_atm, *tail))
         self.form_used = used.value
         self._ms += ms.value
         self._calls += 1
@@ -276,10 +283,22 @@ def kp_vsys_map(values, velocities, phases, Kp, Vsys, v_obs=0.0):
 
 
 def cross_correlate(cc, kind, planets, lam, x=None, engine=None, R_p=None, R_star=None,
-                    offset=None, **kw):
+                    offset=None, broadening=None, **kw):
     """The templates of ``kind`` ("flux", "eclipse" or "transit") of ``x`` (or of ``engine``'s
-    resident spectra) for atmospheres whose stars are ``planets``', through ``cc``."""
+    resident spectra) for atmospheres whose stars are ``planets``', through ``cc``.  With
+    ``broadening`` (a :class:`~frei_amd.broaden.Broadening`, K13) the spectrum — for "transit"
+    minus the depth — is broadened first and stays on the device; the pre-pass follows."""
     from .observe import eclipse_scale, star_library
+    if broadening is not None:
+        if kind not in ("flux", "eclipse", "transit"):
+            raise ValueError(f"unknown kind {kind!r}: 'flux', 'eclipse' or 'transit'")
+        if kind == "eclipse":
+            eclipse_scale(planets, R_p, R_star)     # its errors before any device work
+        if kind == "transit":
+            x = -np.asarray(getattr(x, "value", x), dtype=float)
+        x, engine = broadening.apply(x, engine=engine, keep=True), None
+        if kind == "transit":
+            return cc.correlate(x, offset=offset, **kw)
     if kind == "flux":
         return cc.correlate(x, offset=offset, engine=engine, **kw)
     if kind == "eclipse":

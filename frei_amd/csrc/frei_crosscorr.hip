@@ -503,13 +503,15 @@ int frei_ccf_destroy(frei_ccf* c) {
   return 0;
 }
 
-int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const double* den,
-                   int n_lib, const int32_t* select, const double* scale, const double* offset,
-                   int form, double* sfg, double* sg, double* sgg, int* form_used,
-                   double* kernel_ms) {
+// The three sources of x — a host array, a context's emergent rows, a broadener's kept result
+// (K13) — feed the same src and stride below.
+static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd* brd, int n_atm,
+                          const double* den, int n_lib, const int32_t* select,
+                          const double* scale, const double* offset, int form, double* sfg,
+                          double* sg, double* sgg, int* form_used, double* kernel_ms) {
   if (!c) return set_error("frei_ccf_apply: null handle");
   if (!sfg && !sg && !sgg) return set_error("frei_ccf_apply: sfg, sg and sgg are all null");
-  if (!x && !ctx) return set_error("frei_ccf_apply: x and ctx are both null");
+  if (!x && !ctx && !brd) return set_error("frei_ccf_apply: x and ctx are both null");
   if (n_atm < 1) return set_error("frei_ccf_apply: n_atm must be >= 1");
   if (form < 0 || form > 2)
     return set_error("frei_ccf_apply: form must be 0 (automatic), 1 (VALU) or 2 (fp64 MFMA)");
@@ -521,7 +523,20 @@ int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const
                          std::to_string(select[m]) + " lies outside [0, n_lib = " +
                          std::to_string(n_lib) + ")");
   CtxRows cr{};
-  if (!x) {
+  BrdRows br{};
+  if (brd) {
+    if (int rc = brd_kept_rows(brd, &br)) return rc;
+    if (!br.rows)
+      return set_error("frei_ccf_apply_brd: the broadener holds nothing kept (apply with keep)");
+    if (br.n_lam != c->n_lam)
+      return set_error("frei_ccf_apply_brd: the broadener's n_lam = " + std::to_string(br.n_lam) +
+                       " is not the correlator's " + std::to_string(c->n_lam));
+    if (br.n_atm != n_atm)
+      return set_error("frei_ccf_apply_brd: the broadener keeps " + std::to_string(br.n_atm) +
+                       " atmospheres, not n_atm = " + std::to_string(n_atm));
+    if (br.device != c->device)
+      return set_error("frei_ccf_apply_brd: broadener and correlator live on different devices");
+  } else if (!x) {
     if (int rc = ctx_emergent_rows(ctx, &cr)) return rc;
     if (cr.n_atm != n_atm)
       return set_error("frei_ccf_apply: the context holds " + std::to_string(cr.n_atm) +
@@ -538,7 +553,7 @@ int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const
 
   HIP_TRY(hipSetDevice(c->device));
   // the context's own stream where its spectra are read in place: ordered behind its work
-  hipStream_t st = x ? c->stream : cr.stream;
+  hipStream_t st = (x || brd) ? c->stream : cr.stream;
   const size_t A = (size_t)n_atm, n = (size_t)c->n_lam, V = (size_t)c->n_vel,
                E = (size_t)c->n_exp;
   const bool prepass = den || scale || offset;
@@ -570,8 +585,8 @@ int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const
       rc = set_error("frei_ccf_apply: timing event failed");
   }
   if (!rc) {
-    const double* src = u_x ? u_x : cr.rows;
-    const int64_t xs = u_x ? (int64_t)n : cr.stride;
+    const double* src = u_x ? u_x : brd ? br.rows : cr.rows;
+    const int64_t xs = (u_x || brd) ? (int64_t)n : cr.stride;
     if (prepass)
       ccf_template_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)n_atm), 256, 0, st>>>(
           src, xs, d_den, d_sel, d_scale, d_off, c->n_lam, d_y);
@@ -651,6 +666,23 @@ int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const
     if (p) (void)hipFree(p);
   if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
   return rc;
+}
+
+int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const double* den,
+                   int n_lib, const int32_t* select, const double* scale, const double* offset,
+                   int form, double* sfg, double* sg, double* sgg, int* form_used,
+                   double* kernel_ms) {
+  return ccf_apply_impl(c, ctx, x, nullptr, n_atm, den, n_lib, select, scale, offset, form, sfg,
+                        sg, sgg, form_used, kernel_ms);
+}
+
+int frei_ccf_apply_brd(frei_ccf* c, frei_brd* src, int n_atm, const double* den, int n_lib,
+                       const int32_t* select, const double* scale, const double* offset,
+                       int form, double* sfg, double* sg, double* sgg, int* form_used,
+                       double* kernel_ms) {
+  if (!src) return set_error("frei_ccf_apply_brd: null broadener");
+  return ccf_apply_impl(c, nullptr, nullptr, src, n_atm, den, n_lib, select, scale, offset, form,
+                        sfg, sg, sgg, form_used, kernel_ms);
 }
 
 }  // extern "C"

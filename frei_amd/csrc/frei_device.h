@@ -540,6 +540,17 @@ struct CtxRows {
 };
 int ctx_emergent_rows(frei_ctx* c, CtxRows* out);
 }  // namespace frei
+struct frei_brd;
+namespace frei {
+// K13 (frei_broaden.hip): what the broadener's last apply kept, [n_atm][n_lam] doubles back to
+// back on `device`, complete (its stream was synchronised); rows is null with nothing kept.
+struct BrdRows {
+  const double* rows;
+  int64_t n_lam;
+  int n_atm, device;
+};
+int brd_kept_rows(frei_brd* b, BrdRows* out);
+}  // namespace frei
 struct frei_xsec;
 namespace frei {
 // K6 (frei_binning.hip): bin one species into table rows d_tab + row_off[kp * n_T + kt].

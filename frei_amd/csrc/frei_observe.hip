@@ -296,12 +296,15 @@ int frei_obs_destroy(frei_obs* o) {
   return 0;
 }
 
-int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const double* num,
-                   const double* den, int n_lib, const int32_t* select, const double* scale,
-                   const double* data, const double* sigma, int form, double* obs, double* chi2,
-                   int* form_used, double* kernel_ms) {
+// The three sources of x — a host array, a context's emergent rows, a broadener's kept result
+// (K13) — feed the same x and stride below.
+static int obs_apply_impl(frei_obs* o, frei_ctx* ctx, const double* x, frei_brd* brd, int n_atm,
+                          const double* num, const double* den, int n_lib,
+                          const int32_t* select, const double* scale, const double* data,
+                          const double* sigma, int form, double* obs, double* chi2,
+                          int* form_used, double* kernel_ms) {
   if (!o || !obs) return set_error("frei_obs_apply: null handle or null obs");
-  if (!x && !ctx) return set_error("frei_obs_apply: x and ctx are both null");
+  if (!x && !ctx && !brd) return set_error("frei_obs_apply: x and ctx are both null");
   if (n_atm < 1) return set_error("frei_obs_apply: n_atm must be >= 1");
   if (form < 0 || form > 2)
     return set_error("frei_obs_apply: form must be 0 (automatic), 1 (lane per channel) or 2 "
@@ -322,7 +325,20 @@ int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const
                          "] must be > 0 (+inf removes the channel)");
   }
   CtxRows cr{};
-  if (!x) {
+  BrdRows br{};
+  if (brd) {
+    if (int rc = brd_kept_rows(brd, &br)) return rc;
+    if (!br.rows)
+      return set_error("frei_obs_apply_brd: the broadener holds nothing kept (apply with keep)");
+    if (br.n_lam != o->n_lam)
+      return set_error("frei_obs_apply_brd: the broadener's n_lam = " + std::to_string(br.n_lam) +
+                       " is not the instrument's " + std::to_string(o->n_lam));
+    if (br.n_atm != n_atm)
+      return set_error("frei_obs_apply_brd: the broadener keeps " + std::to_string(br.n_atm) +
+                       " atmospheres, not n_atm = " + std::to_string(n_atm));
+    if (br.device != o->device)
+      return set_error("frei_obs_apply_brd: broadener and instrument live on different devices");
+  } else if (!x) {
     if (int rc = ctx_emergent_rows(ctx, &cr)) return rc;
     if (cr.n_atm != n_atm)
       return set_error("frei_obs_apply: the context holds " + std::to_string(cr.n_atm) +
@@ -340,7 +356,7 @@ int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const
 
   HIP_TRY(hipSetDevice(o->device));
   // the context's own stream where its spectra are read in place: ordered behind its work
-  hipStream_t st = x ? o->stream : cr.stream;
+  hipStream_t st = (x || brd) ? o->stream : cr.stream;
   const size_t A = (size_t)n_atm, n = (size_t)o->n_lam, K = (size_t)o->K;
   double *u_x = nullptr, *d_num = nullptr, *d_den = nullptr, *d_scale = nullptr,
          *d_data = nullptr, *d_sigma = nullptr, *d_obs = nullptr, *d_chi2 = nullptr;
@@ -367,8 +383,8 @@ int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const
   }
   if (!rc) {
     ObsArgs a;
-    a.x = u_x ? u_x : cr.rows;
-    a.xs = u_x ? (int64_t)n : cr.stride;
+    a.x = u_x ? u_x : brd ? br.rows : cr.rows;
+    a.xs = (u_x || brd) ? (int64_t)n : cr.stride;
     a.num = d_num;
     a.den = d_den;
     a.select = d_sel;
@@ -412,6 +428,23 @@ int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const
     if (p) (void)hipFree(p);
   if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
   return rc;
+}
+
+int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const double* num,
+                   const double* den, int n_lib, const int32_t* select, const double* scale,
+                   const double* data, const double* sigma, int form, double* obs, double* chi2,
+                   int* form_used, double* kernel_ms) {
+  return obs_apply_impl(o, ctx, x, nullptr, n_atm, num, den, n_lib, select, scale, data, sigma,
+                        form, obs, chi2, form_used, kernel_ms);
+}
+
+int frei_obs_apply_brd(frei_obs* o, frei_brd* src, int n_atm, const double* num,
+                       const double* den, int n_lib, const int32_t* select, const double* scale,
+                       const double* data, const double* sigma, int form, double* obs,
+                       double* chi2, int* form_used, double* kernel_ms) {
+  if (!src) return set_error("frei_obs_apply_brd: null broadener");
+  return obs_apply_impl(o, nullptr, nullptr, src, n_atm, num, den, n_lib, select, scale, data,
+                        sigma, form, obs, chi2, form_used, kernel_ms);
 }
 
 }  // extern "C"

@@ -230,11 +230,16 @@ class Instrument:
         channel).  ``num`` and ``den`` are optional libraries ([n_lam] or [n_lib][n_lam]),
         ``select`` [n_atm] the library row of each atmosphere (default row 0), ``scale`` a
         factor per atmosphere.  ``x=None`` with ``engine=`` (an Engine or BatchEngine on the
-        whole axis) takes the emergent spectra resident in the engine's flux state.  ``form``
+        whole axis) takes the emergent spectra resident in the engine's flux state; a
+        :class:`~frei_amd.broaden.BroadenedSpectra` as ``x`` takes what
+        ``Broadening.apply(keep=True)`` left on the device.  ``form``
         0 picks the kernel from the points per channel, 1 forces one lane per channel, 2 one
         group of lanes per channel (``form_used`` records the choice)."""
-        ctx = None
-        if x is None:
+        ctx, brd = None, None
+        if hasattr(x, "owner") and hasattr(x, "serial"):
+            # a BroadenedSpectra (K13): the spectra lie on the device with its Broadening
+            brd, n_atm, single, x = x.handle(), x.n_atm, x.single, None
+        elif x is None:
             if engine is None:
                 raise ValueError("pass x, or engine= for its resident spectra")
             if engine.n_lam != engine.lam_um.size:
@@ -275,11 +280,14 @@ class Instrument:
             chi2 = np.empty(n_atm)
         obs = np.empty((n_atm, K))
         used, ms = ctypes.c_int(0), ctypes.c_double(0.0)
-        N.check(N.lib().frei_obs_apply(
-            self.handle(), ctx, N.dptr(x), n_atm, N.dptr(num), N.dptr(den), n_lib,
-            None if sel is None else sel.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-            N.dptr(sc), N.dptr(data), N.dptr(sigma), int(form), N.dptr(obs), N.dptr(chi2),
-            ctypes.byref(used), ctypes.byref(ms)))
+        tail = (N.dptr(num), N.dptr(den), n_lib,
+                None if sel is None else sel.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                N.dptr(sc), N.dptr(data), N.dptr(sigma), int(form), N.dptr(obs), N.dptr(chi2),
+                ctypes.byref(used), ctypes.byref(ms))
+        if brd is not None:
+            N.check(N.lib().frei_obs_apply_brd(self.handle(), brd, n_atm, *tail))
+        else:
+            N.check(N.lib().frei_obs_apply(self.handle(), ctx, N.dptr(x), n_atm, *tail))
         self.form_used = used.value
         self._ms += ms.value
         self._calls += 1
@@ -319,9 +327,17 @@ def eclipse_scale(planets, R_p, R_star):
 
 
 def observe(instrument, kind, planets, lam, x=None, engine=None, weighting=None, data=None,
-            sigma=None, R_p=None, R_star=None):
+            sigma=None, R_p=None, R_star=None, broadening=None):
     """The observable ``kind`` ("flux", "eclipse" or "transit") of ``x`` (or of ``engine``'s
-    resident spectra) for atmospheres whose stars are ``planets``'."""
+    resident spectra) for atmospheres whose stars are ``planets``'.  With ``broadening`` (a
+    :class:`~frei_amd.broaden.Broadening`, K13) the spectrum is broadened first and stays on the
+    device."""
+    if broadening is not None:
+        if kind not in ("flux", "eclipse", "transit"):
+            raise ValueError(f"unknown kind {kind!r}: 'flux', 'eclipse' or 'transit'")
+        if kind == "eclipse":
+            eclipse_scale(planets, R_p, R_star)     # its errors before any device work
+        x, engine = broadening.apply(x, engine=engine, keep=True), None
     kw = dict(data=data, sigma=sigma, engine=engine)
     if kind == "flux":
         return instrument.apply(x, **kw)

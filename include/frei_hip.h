@@ -611,6 +611,101 @@ int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const
                    double* kernel_ms);
 int frei_ccf_destroy(frei_ccf* c);
 
+/*
+ * Broadening (K13): batched native-resolution spectra convolved with a kernel tabulated in
+ * velocity (a planet's rotation, an instrument's line-spread function, or both).  The reference
+ * has no counterpart; this is the definition.
+ * A broadener on a native axis lam[n_lam] (strictly ascending, n_lam >= 2) holds, resident on
+ * `device` with the handle:
+ *   u[j] = c ln(lam[j]), c = 299792.458 km/s, formed on the host and passed in (never recomputed
+ *     on the device);
+ *   tw[j], the trapezoid weights of the axis in u: half the neighbouring gaps, one-sided at the
+ *     ends;
+ *   the kernel table tab[n_tab], n_tab odd and >= 3, h = (n_tab - 1) / 2, every value finite and
+ *     >= 0, sampled at the velocities (k - h) dv, dv > 0: its half-width is H = h * dv;
+ *   the window of every output i, first[i] and count[i]: the contiguous run of j with
+ *     |u[j] - u[i]| <= H, decided with that very subtraction in fp64.  It contains i and is
+ *     truncated at the ends of the axis (no padding, no wrap);
+ *   norm[i], below.
+ * The weight of input j in output i, by exactly these IEEE operations (never contracted):
+ *   d = u[j] - u[i];  q = d * inv_dv + h;  k = clamp(floor(q), 0, n_tab - 2);  f = q - k
+ *   K = tab[k] + f * (tab[k+1] - tab[k]);  w_ij = tw[j] * K
+ * with inv_dv = 1 / dv formed once on the host and passed in.
+ *   norm[i] = sum_j w_ij over the window, ascending j, plain additions; frei_brd_create forms it
+ *     on the host and uploads it (frei_brd_norm reads it back).
+ *   out[m][i] = (sum_j w_ij * x[m][j]) / norm[i]: every term enters by one fused multiply-add,
+ *     one division at the end.  Renormalising over the truncated window is the edge rule.
+ * frei_brd_create checks on the host, before it touches a device, naming the first offending
+ * index: u finite and strictly ascending, tw finite and >= 0, dv and inv_dv > 0, n_tab odd and
+ * >= 3, the table finite and >= 0, every window on the axis, holding its own point, agreeing
+ * with the criterion above (its two ends within H, the points just outside not) and of at most
+ * FREI_BRD_MAX_COUNT points, every norm[i] finite and > 0.
+ */
+#define FREI_BRD_MAX_COUNT 4096
+typedef struct frei_brd frei_brd;
+int frei_brd_create(frei_brd** out, int device, int64_t n_lam, const double* u, const double* tw,
+                    const int32_t* first, const int32_t* count, int n_tab, double dv,
+                    double inv_dv, const double* tab);
+/* norm[n_lam] as frei_brd_create formed it. */
+int frei_brd_norm(frei_brd* b, double* norm);
+/*
+ * Broaden x[n_atm][n_lam], a host array (uploaded for the call), or NULL with a context: the
+ * source is then the emergent row F_up[n_layers - 1] of every atmosphere, in place in the flux
+ * state on the context's stream, under the rules of frei_obs_apply and frei_ccf_apply (n_atm ==
+ * the context's atmosphere count, n_lam == its n_lam, the same device; a context of a wavelength
+ * slice does not fit: a window may straddle slices).
+ * out[n_atm][n_lam] receives the result; it may be NULL when keep is set.  With keep != 0 the
+ * result also stays in a device buffer the handle owns until the next frei_brd_apply (kept or
+ * not, successful or not once its arguments are accepted) or frei_brd_destroy;
+ * frei_ccf_apply_brd and frei_obs_apply_brd read it there.
+ * Order of summation:
+ *   form 1 (VALU): one lane per output i; the taps j = first[i] .. first[i] + count[i] - 1 in
+ *     ascending order, acc = fma(w_ij, x[m][j], acc) from acc = 0.
+ *   form 2 (fp64 MFMA, v_mfma_f64_16x16x4_f64): tiles of the 16 consecutive outputs i0 .. i0 +
+ *     15 (i0 a multiple of 16) x 16 atmospheres.  The tile's span is jlo = first[i0] to jhi =
+ *     first[il] + count[il], il = min(i0 + 15, n_lam - 1): the union of its windows.  Step s = 0,
+ *     1, ... while jlo + 4 s < jhi, ascending, adds the points jlo + 4 s + (0 .. 3) in the matrix
+ *     unit: A = 16 outputs x 4 points of weights, each lane forming its own w_ij, exactly 0 where
+ *     j lies outside that output's own window (and for outputs past the axis); B = 4 points x 16
+ *     atmospheres of x, 0 for points at or past jhi and for atmospheres at or past n_atm.  x
+ *     reaches B through LDS in chunks of 64 points from jlo (read in rows of consecutive points);
+ *     the trailing steps of a chunk that begin at or past jhi are not taken.
+ *   form 0 picks form 2 from 5 atmospheres on where the windows hold 21 points or more on
+ *     average (sum of count / n_lam) and from 2 atmospheres on where they hold 81 or more, form
+ *     1 otherwise: the measured crossover
+ *     (tools/broaden_probe.py, profiles/r12/broaden/README.md); *form_used receives the form
+ *     that ran.
+ * No atomics; for a given form and handle the order of every sum is fixed: results are bitwise
+ * the same from call to call, and row m of a batched call is bitwise the call on that row alone.
+ * Form 1 returns a spectrum that is constant at 1 or any other power of two exactly: numerator
+ * and norm are then the same sum (scaled exactly).  Non-finite input: form 1 carries a NaN or inf
+ * in x[m][j] to exactly the outputs i of row m whose window holds j.  Form 2 carries it to those
+ * and, because 0 * NaN enters the product (B is not masked), to every other output of a 16-output
+ * tile whose span [jlo, jhi) holds j — of row m alone; other rows and tiles are untouched.
+ * Nothing in x is checked.
+ * *form_used and *kernel_ms (HIP events around the kernel only) may be NULL.  Errors (handle and
+ * context stay usable): null handle, x and ctx both null, out null without keep, a context of
+ * another shape or device.
+ */
+int frei_brd_apply(frei_brd* b, frei_ctx* ctx, const double* x, int n_atm, int form,
+                   double* out, int keep, int* form_used, double* kernel_ms);
+int frei_brd_destroy(frei_brd* b);
+/*
+ * frei_ccf_apply and frei_obs_apply with the result `src` kept (frei_brd_apply with keep) as
+ * their x: a third source beside the host array and the context, read where it lies.  The other
+ * arguments and the results are those of frei_ccf_apply / frei_obs_apply, bitwise what they give
+ * for a host copy of the same numbers.  Errors: a null broadener, one with nothing kept, or one
+ * of another n_lam, n_atm or device.
+ */
+int frei_ccf_apply_brd(frei_ccf* c, frei_brd* src, int n_atm, const double* den, int n_lib,
+                       const int32_t* select, const double* scale, const double* offset,
+                       int form, double* sfg, double* sg, double* sgg, int* form_used,
+                       double* kernel_ms);
+int frei_obs_apply_brd(frei_obs* o, frei_brd* src, int n_atm, const double* num,
+                       const double* den, int n_lib, const int32_t* select, const double* scale,
+                       const double* data, const double* sigma, int form, double* obs,
+                       double* chi2, int* form_used, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
