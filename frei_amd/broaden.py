@@ -20,6 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from ._device import DeviceObject, i32ptr, resident_or_host
 from .crosscorr import C_KMS
 from .units import value
 
@@ -46,7 +47,6 @@ def automatic_form(n_atm, mean_points):
                  (n_atm >= 2 and mean_points >= MFMA_WIDE_POINTS)) else 1
 
 
-_i32p = ctypes.POINTER(ctypes.c_int32)
 _FWHM = 2.0 * np.sqrt(2.0 * np.log(2.0))      # FWHM of a Gaussian in standard deviations
 
 
@@ -201,13 +201,16 @@ class BroadenedSpectra:
         return self.owner._handle
 
 
-class Broadening:
+class Broadening(DeviceObject):
     """``kernel`` (:class:`BroadeningKernel`) on the native axis ``lam`` ([n_lam], µm or a
     Quantity, strictly ascending).  The plan is built on the host, vectorised: ``u``, ``tw``,
     ``first``, ``count`` (and ``norm``, computed on first use by the device library's
     operations) are exposed for inspection."""
 
+    _destroy = "frei_brd_destroy"
+
     def __init__(self, lam, kernel, device=0):
+        super().__init__(device)
         self.lam = N.f64(value(lam, "um"))
         if self.lam.ndim != 1 or self.lam.size < 2:
             raise ValueError("lam must be a 1-D wavelength axis of at least 2 points")
@@ -220,13 +223,8 @@ class Broadening:
         self.u = N.f64(C_KMS * np.log(self.lam))
         self.tw = axis_weights(self.u)
         self.first, self.count = windows(self.u, kernel.half_width)
-        self.device = device
-        self.form_used = None
         self._norm = None
-        self._handle = None
         self._serial = 0
-        self._ms = 0.0
-        self._calls = 0
 
     @property
     def n_lam(self):
@@ -247,16 +245,12 @@ class Broadening:
         return self._norm
 
     # ------------------------------------------------------------------ device
-    def handle(self):
+    def _create(self, h):
         """frei_brd* of the broadener (axis, windows, norm and table uploaded once)."""
-        if self._handle is None:
-            h = ctypes.c_void_p()
-            N.check(N.lib().frei_brd_create(
-                ctypes.byref(h), self.device, self.n_lam, N.dptr(self.u), N.dptr(self.tw),
-                self.first.ctypes.data_as(_i32p), self.count.ctypes.data_as(_i32p),
-                self.tab.size, self.dv, self.inv_dv, N.dptr(self.tab)))
-            self._handle = h
-        return self._handle
+        return N.lib().frei_brd_create(
+            ctypes.byref(h), self.device, self.n_lam, N.dptr(self.u), N.dptr(self.tw),
+            i32ptr(self.first), i32ptr(self.count), self.tab.size, self.dv, self.inv_dv,
+            N.dptr(self.tab))
 
     def device_norm(self):
         """``norm`` as ``frei_brd_create`` formed it (read back from the device)."""
@@ -265,24 +259,8 @@ class Broadening:
         return out
 
     def release(self):
-        self._serial += 1
-        if self._handle is not None:
-            N.lib().frei_brd_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def timing(self, reset=False):
-        """(milliseconds, calls) of the kernels since the last reset (HIP events around the
-        kernels only: uploads and read-back excluded)."""
-        ms, n = self._ms, self._calls
-        if reset:
-            self._ms, self._calls = 0.0, 0
-        return ms, n
+        self._serial += 1     # whatever was kept ends with the handle
+        super().release()
 
     def apply(self, x=None, engine=None, form=0, keep=False):
         """``x`` ([n_lam] or [n_atm][n_lam]) broadened -> an array of the same shape (a
@@ -292,33 +270,17 @@ class Broadening:
         (``form_used`` records the choice).  ``keep=True`` leaves the result on the device and
         returns a :class:`BroadenedSpectra` for ``CrossCorrelator.correlate`` or
         ``Instrument.apply``; nothing is copied back."""
-        ctx, unit = None, None
-        if x is None:
-            if engine is None:
-                raise ValueError("pass x, or engine= for its resident spectra")
-            if engine.n_lam != engine.lam_um.size:
-                raise ValueError("a wavelength-slice engine cannot feed a broadener: a window "
-                                 "may straddle slices")
-            ctx = engine._ctx
-            n_atm, single = getattr(engine, "n_atm", 1), not hasattr(engine, "n_atm")
-        else:
-            unit = getattr(x, "unit", None)
-            x = N.f64(getattr(x, "value", x))     # a Quantity's numbers as they are
-            if x.ndim not in (1, 2) or x.shape[-1] != self.n_lam:
-                raise ValueError(f"x must be [n_lam] or [n_atm][n_lam] with n_lam = "
-                                 f"{self.n_lam}, not {x.shape}")
-            single = x.ndim == 1
-            x = np.ascontiguousarray(np.atleast_2d(x))
-            n_atm = x.shape[0]
+        x, ctx, brd, n_atm, single, unit = resident_or_host(
+            x, engine, self.n_lam, ("a broadener", "a window"))
+        if brd is not None:
+            raise TypeError("a BroadenedSpectra cannot be broadened again: pass an array")
         out = None if keep else np.empty((n_atm, self.n_lam))
         used, ms = ctypes.c_int(0), ctypes.c_double(0.0)
         handle = self.handle()
         self._serial += 1                          # whatever was kept ends with this call
         N.check(N.lib().frei_brd_apply(handle, ctx, N.dptr(x), n_atm, int(form), N.dptr(out),
                                        1 if keep else 0, ctypes.byref(used), ctypes.byref(ms)))
-        self.form_used = used.value
-        self._ms += ms.value
-        self._calls += 1
+        self._record(used, ms)
         if keep:
             return BroadenedSpectra(self, self._serial, n_atm, single)
         if single:

@@ -21,6 +21,8 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from ._device import (DeviceObject, broadened_source, i32ptr, library_rows, per_atmosphere,
+                      resident_or_host, select_rows, unknown_kind)
 from .units import value
 
 __all__ = ["CrossCorrelator", "CrossCorrelation", "kp_vsys_map", "FORMS", "PIXEL_CHUNK",
@@ -32,7 +34,6 @@ FORMS = (1, 2)
 # pixels per chunk of the device sums (frei_crosscorr.hip kChunk): the order of summation
 # changes at its multiples
 PIXEL_CHUNK = 4096
-_i32p = ctypes.POINTER(ctypes.c_int32)
 _SUMS = ("sfg", "sg", "sgg")
 
 
@@ -92,7 +93,7 @@ class CrossCorrelation:
         return -(self.n_pix / 2.0) * np.log((V_f - 2.0 * C_fg + V_g) / self.W)
 
 
-class CrossCorrelator:
+class CrossCorrelator(DeviceObject):
     """High-resolution data against Doppler-shifted templates on the native axis ``lam``
     ([n_lam], µm or a Quantity, strictly ascending).  ``wl_data`` [n_pix] (µm) in any order
     (several spectral orders back to back, overlapping or not), ``flux`` [n_exp][n_pix] or
@@ -101,7 +102,10 @@ class CrossCorrelator:
     Beyond the axis the template is held constant; ``n_clamped`` [n_vel] counts the pixels for
     which that happened, so a caller can drop those velocities."""
 
+    _destroy = "frei_ccf_destroy"
+
     def __init__(self, lam, wl_data, flux, velocities, weights=None, device=0):
+        super().__init__(device)
         self.lam = N.f64(value(lam, "um"))
         if self.lam.ndim != 1 or self.lam.size < 2:
             raise ValueError("lam must be a 1-D wavelength axis of at least 2 points")
@@ -128,11 +132,6 @@ class CrossCorrelator:
         self.W = float(np.sum(self.weights))
         self.S_wf = np.sum(self.a, axis=1)
         self.S_wff = np.sum(self.a * self.flux, axis=1)
-        self.device = device
-        self.form_used = None
-        self._handle = None
-        self._ms = 0.0
-        self._calls = 0
 
     @property
     def n_lam(self):
@@ -151,35 +150,11 @@ class CrossCorrelator:
         return self.flux.shape[0]
 
     # ------------------------------------------------------------------ device
-    def handle(self):
+    def _create(self, h):
         """frei_ccf* of the correlator (plan, data and weights uploaded once)."""
-        if self._handle is None:
-            h = ctypes.c_void_p()
-            N.check(N.lib().frei_ccf_create(
-                ctypes.byref(h), self.device, self.n_lam, self.n_pix, self.n_vel,
-                self.idx.ctypes.data_as(_i32p), N.dptr(self.frac), self.n_exp, N.dptr(self.a),
-                N.dptr(self.weights)))
-            self._handle = h
-        return self._handle
-
-    def release(self):
-        if self._handle is not None:
-            N.lib().frei_ccf_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def timing(self, reset=False):
-        """(milliseconds, calls) of the kernels since the last reset (HIP events around the
-        kernels only: uploads and read-back excluded)."""
-        ms, n = self._ms, self._calls
-        if reset:
-            self._ms, self._calls = 0.0, 0
-        return ms, n
+        return N.lib().frei_ccf_create(
+            ctypes.byref(h), self.device, self.n_lam, self.n_pix, self.n_vel, i32ptr(self.idx),
+            N.dptr(self.frac), self.n_exp, N.dptr(self.a), N.dptr(self.weights))
 
     def correlate(self, x, den=None, select=None, scale=None, offset=None, form=0, engine=None,
                   want=_SUMS):
@@ -197,59 +172,25 @@ class CrossCorrelator:
         want = (want,) if isinstance(want, str) else tuple(want)
         if any(k not in _SUMS for k in want):
             raise ValueError(f"want holds names other than {_SUMS}: {want}")
-        ctx, brd = None, None
-        if hasattr(x, "owner") and hasattr(x, "serial"):
-            # a BroadenedSpectra (K13): the spectra lie on the device with its Broadening
-            brd, n_atm, single, x = x.handle(), x.n_atm, x.single, None
-        elif x is None:
-            if engine is None:
-                raise ValueError("pass x, or engine= for its resident spectra")
-            if engine.n_lam != engine.lam_um.size:
-                raise ValueError("a wavelength-slice engine cannot feed a correlator: a "
-                                 "pixel's bracket may straddle slices")
-            ctx = engine._ctx
-            n_atm, single = getattr(engine, "n_atm", 1), not hasattr(engine, "n_atm")
-        else:
-            x = N.f64(getattr(x, "value", x))     # a Quantity's numbers as they are
-            if x.ndim not in (1, 2) or x.shape[-1] != self.n_lam:
-                raise ValueError(f"x must be [n_lam] or [n_atm][n_lam] with n_lam = "
-                                 f"{self.n_lam}, not {x.shape}")
-            single = x.ndim == 1
-            x = np.ascontiguousarray(np.atleast_2d(x))
-            n_atm = x.shape[0]
-        n_lib = 0
-        if den is not None:
-            den = np.ascontiguousarray(np.atleast_2d(N.f64(getattr(den, "value", den))))
-            if den.ndim != 2 or den.shape[1] != self.n_lam:
-                raise ValueError(f"den must be [n_lam] or [n_lib][n_lam] with n_lam = "
-                                 f"{self.n_lam}, not {den.shape}")
-            n_lib = den.shape[0]
-        sel = None
-        if select is not None:
-            sel = np.ascontiguousarray(select, dtype=np.int32)
-            if sel.shape != (n_atm,):
-                raise ValueError(f"select must have {n_atm} entries")
-
-        def per_atm(v):
-            if v is None:
-                return None
-            return N.f64(np.broadcast_to(np.asarray(v, dtype=float), (n_atm,)))
-        sc, off = per_atm(scale), per_atm(offset)
+        x, ctx, brd, n_atm, single, _ = resident_or_host(
+            x, engine, self.n_lam, ("a correlator", "a pixel's bracket"))
+        den = library_rows(den, "den", self.n_lam)
+        n_lib = 0 if den is None else den.shape[0]
+        sel = select_rows(select, n_atm)
+        sc, off = per_atmosphere(scale, n_atm), per_atmosphere(offset, n_atm)
         V, E = self.n_vel, self.n_exp
         out = dict(sfg=np.empty((n_atm, E, V)) if "sfg" in want else None,
                    sg=np.empty((n_atm, V)) if "sg" in want else None,
                    sgg=np.empty((n_atm, V)) if "sgg" in want else None)
         used, ms = ctypes.c_int(0), ctypes.c_double(0.0)
-        tail = (N.dptr(den), n_lib, None if sel is None else sel.ctypes.data_as(_i32p),
-                N.dptr(sc), N.dptr(off), int(form), N.dptr(out["sfg"]), N.dptr(out["sg"]),
-                N.dptr(out["sgg"]), ctypes.byref(used), ctypes.byref(ms))
+        tail = (N.dptr(den), n_lib, i32ptr(sel), N.dptr(sc), N.dptr(off), int(form),
+                N.dptr(out["sfg"]), N.dptr(out["sg"]), N.dptr(out["sgg"]), ctypes.byref(used),
+                ctypes.byref(ms))
         if brd is not None:
             N.check(N.lib().frei_ccf_apply_brd(self.handle(), brd, n_atm, *tail))
         else:
             N.check(N.lib().frei_ccf_apply(self.handle(), ctx, N.dptr(x), n_atm, *tail))
-        self.form_used = used.value
-        self._ms += ms.value
-        self._calls += 1
+        self._record(used, ms)
         if single:
             out = {k: None if v is None else v[0] for k, v in out.items()}
         return CrossCorrelation(out["sfg"], out["sg"], out["sgg"], self.velocities, self.W,
@@ -288,25 +229,11 @@ def cross_correlate(cc, kind, planets, lam, x=None, engine=None, R_p=None, R_sta
     resident spectra) for atmospheres whose stars are ``planets``', through ``cc``.  With
     ``broadening`` (a :class:`~frei_amd.broaden.Broadening`, K13) the spectrum — for "transit"
     minus the depth — is broadened first and stays on the device; the pre-pass follows."""
-    from .observe import eclipse_scale, star_library
-    if broadening is not None:
-        if kind not in ("flux", "eclipse", "transit"):
-            raise ValueError(f"unknown kind {kind!r}: 'flux', 'eclipse' or 'transit'")
-        if kind == "eclipse":
-            eclipse_scale(planets, R_p, R_star)     # its errors before any device work
-        if kind == "transit":
-            x = -np.asarray(getattr(x, "value", x), dtype=float)
-        x, engine = broadening.apply(x, engine=engine, keep=True), None
-        if kind == "transit":
-            return cc.correlate(x, offset=offset, **kw)
-    if kind == "flux":
-        return cc.correlate(x, offset=offset, engine=engine, **kw)
-    if kind == "eclipse":
-        scale = eclipse_scale(planets, R_p, R_star)     # before any device work
-        lib, select = star_library(planets, lam)
-        return cc.correlate(x, den=lib, select=select, scale=scale, offset=offset,
-                            engine=engine, **kw)
+    if kind == "transit":     # minus the depth, before any broadening
+        x = -np.asarray(getattr(x, "value", x), dtype=float)
+    x, engine, star = broadened_source(kind, planets, lam, x, engine, R_p, R_star, broadening)
     if kind == "transit":
-        return cc.correlate(-np.asarray(getattr(x, "value", x), dtype=float), offset=offset,
-                            **kw)
-    raise ValueError(f"unknown kind {kind!r}: 'flux', 'eclipse' or 'transit'")
+        return cc.correlate(x, offset=offset, **kw)
+    if kind in ("flux", "eclipse"):
+        return cc.correlate(x, offset=offset, engine=engine, **star, **kw)
+    raise unknown_kind(kind)

@@ -26,7 +26,7 @@
 #include <vector>
 
 #include "../../include/frei_hip.h"
-#include "frei_device.h"
+#include "frei_host.h"
 
 using namespace frei;
 
@@ -58,28 +58,6 @@ constexpr int kExactRows = 8;     // source rows per block in the exact mode
 constexpr int kGroupiesRows = 8;  // source rows per lane in the groupies pass
 constexpr int kGroupiesBatch = 4; // of which summed together (loads in flight)
 
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) return set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-#define TRY(expr)            \
-  do {                       \
-    int _r = (expr);         \
-    if (_r != 0) return _r;  \
-  } while (0)
-
-template <typename T>
-int dalloc(T** p, size_t n) {
-  if (n == 0) n = 1;
-  HIP_TRY(hipMalloc((void**)p, n * sizeof(T)));
-  return 0;
-}
-template <typename T>
-void dfree(T*& p) {
-  if (p) (void)hipFree((void*)p);
-  p = nullptr;
-}
 // Plan array `slot` of x on the device (grown when too small) holding h.
 template <typename T>
 int stage(frei_xsec* x, int slot, T** d, const std::vector<T>& h, hipStream_t st) {

@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "../../include/frei_hip.h"
-#include "frei_device.h"
+#include "frei_host.h"
 
 using namespace frei;
 
@@ -58,12 +58,6 @@ constexpr int kChunkJ = 64;  // form 2: points of x staged per turn (16 MFMA ste
 constexpr int kMfmaFromAtmospheres = 5;
 constexpr double kMfmaFromPoints = 21.0;
 constexpr double kMfmaWidePoints = 81.0;
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) return set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 // The weight of input j in output i: exactly these operations, none contracted (the library is
 // built with -ffp-contract=off).  d = u[j] - u[i].
@@ -349,18 +343,9 @@ int frei_brd_apply(frei_brd* b, frei_ctx* ctx, const double* x, int n_atm, int f
   if (n_atm < 1) return set_error("frei_brd_apply: n_atm must be >= 1");
   if (form < 0 || form > 2)
     return set_error("frei_brd_apply: form must be 0 (automatic), 1 (VALU) or 2 (fp64 MFMA)");
-  CtxRows cr{};
-  if (!x) {
-    if (int rc = ctx_emergent_rows(ctx, &cr)) return rc;
-    if (cr.n_atm != n_atm)
-      return set_error("frei_brd_apply: the context holds " + std::to_string(cr.n_atm) +
-                       " atmospheres, not n_atm = " + std::to_string(n_atm));
-    if (cr.n_lam != b->n_lam)
-      return set_error("frei_brd_apply: the context's n_lam = " + std::to_string(cr.n_lam) +
-                       " is not the broadener's " + std::to_string(b->n_lam));
-    if (cr.device != b->device)
-      return set_error("frei_brd_apply: context and broadener live on different devices");
-  }
+  SpectrumRows src;
+  TRY(spectrum_rows(x, ctx, nullptr, n_atm, b->n_lam, b->device, b->stream, "broadener",
+                    "frei_brd_apply", &src));
   int f = form;
   if (f == 0)
     f = (n_atm >= kMfmaFromAtmospheres && b->mean_points >= kMfmaFromPoints) ||
@@ -377,36 +362,21 @@ int frei_brd_apply(frei_brd* b, frei_ctx* ctx, const double* x, int n_atm, int f
     b->d_keep = nullptr;
     b->keep_atm = 0;
   }
-  // the context's own stream where its spectra are read in place: ordered behind its work
-  hipStream_t st = x ? b->stream : cr.stream;
+  hipStream_t st = src.stream;
   const size_t A = (size_t)n_atm, n = (size_t)b->n_lam;
   // form 1: 1, 4 or 8 atmospheres per lane; form 2: blocks of 16 atmospheres
   const int bt = n_atm == 1 ? 1 : n_atm <= 4 ? 4 : 8;
   const int cb = (n_atm + 15) / 16;
   if ((n_atm + bt - 1) / bt > 65535)
     return set_error("frei_brd_apply: n_atm exceeds the launch grid");
-  double *u_x = nullptr, *d_out = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int rc = 0;
-  auto try_hip = [&](hipError_t e, const char* what) {
-    if (e != hipSuccess && !rc) rc = set_error(std::string(what) + ": " + hipGetErrorString(e));
-  };
-  if (x) {
-    try_hip(hipMalloc((void**)&u_x, A * n * sizeof(double)), "frei_brd_apply: allocation");
-    if (!rc)
-      try_hip(hipMemcpyAsync(u_x, x, A * n * sizeof(double), hipMemcpyHostToDevice, st),
-              "frei_brd_apply: upload");
-  }
-  if (!rc) try_hip(hipMalloc((void**)&d_out, A * n * sizeof(double)), "frei_brd_apply: allocation");
-  if (!rc && kernel_ms) {
-    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess ||
-        hipEventRecord(ev[0], st) != hipSuccess)
-      rc = set_error("frei_brd_apply: timing event failed");
-  }
-  if (!rc) {
+  DeviceCall call(st, "broadening");
+  const double* u_x = call.upload(x, A * n);
+  double* d_out = call.alloc<double>(A * n);
+  call.begin(kernel_ms);
+  if (call.ok()) {
     BrdArgs a;
-    a.x = u_x ? u_x : cr.rows;
-    a.xs = u_x ? (int64_t)n : cr.stride;
+    a.x = u_x ? u_x : src.rows;
+    a.xs = src.stride;
     a.n = b->n_lam;
     a.u = b->d_u;
     a.tw = b->d_tw;
@@ -428,30 +398,15 @@ int frei_brd_apply(frei_brd* b, frei_ctx* ctx, const double* x, int n_atm, int f
     } else {
       brd_mfma_kernel<<<g2, 64, 0, st>>>(a);
     }
-    if (hipGetLastError() != hipSuccess) rc = set_error("broadening kernel launch failed");
   }
-  if (!rc && kernel_ms) {
-    float ms = 0;
-    if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
-        hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess)
-      rc = set_error("frei_brd_apply: timing event failed");
-    else
-      *kernel_ms = ms;
-  }
-  if (!rc && out)
-    try_hip(hipMemcpyAsync(out, d_out, A * n * sizeof(double), hipMemcpyDeviceToHost, st),
-            "frei_brd_apply: read-back");
-  if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_error("broadening kernel failed");
-  for (auto& e : ev)
-    if (e) (void)hipEventDestroy(e);
-  if (u_x) (void)hipFree(u_x);
+  call.end();
+  call.download(out, d_out, A * n);
+  if (keep) call.keep(d_out);
+  const int rc = call.finish();
   if (!rc && keep) {
-    b->d_keep = d_out;   // complete: the stream was synchronised above
+    b->d_keep = d_out;   // complete: finish() synchronised the stream
     b->keep_atm = n_atm;
-  } else if (d_out) {
-    (void)hipFree(d_out);
   }
-  if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
   return rc;
 }
 

@@ -29,7 +29,7 @@
 #include <vector>
 
 #include "../../include/frei_hip.h"
-#include "frei_device.h"
+#include "frei_host.h"
 
 using namespace frei;
 
@@ -62,12 +62,6 @@ constexpr int kEPad = 16;     // aT's rows are padded to whole MFMA exposure blo
 // up with every tile of 8 exposures, the MFMA form with every block of 16; they cross where the
 // VALU form takes its second tile.
 constexpr int kMfmaFromExposures = 9;
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) return set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 struct CcfArgs {
   const double* y;        // row m at y + m * ys
@@ -386,18 +380,6 @@ __global__ __launch_bounds__(256) void ccf_combine_kernel(const double* __restri
   out[i] = s;
 }
 
-template <typename T>
-int dalloc(T** p, size_t n) {
-  HIP_TRY(hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
-  return 0;
-}
-
-template <typename T>
-int h2d(T* d, const T* h, size_t n, hipStream_t st) {
-  HIP_TRY(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-  return 0;
-}
-
 std::string at2(const char* name, int64_t i, int64_t k) {
   return std::string(name) + "[" + std::to_string(i) + "][" + std::to_string(k) + "]";
 }
@@ -516,77 +498,40 @@ static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd*
   if (form < 0 || form > 2)
     return set_error("frei_ccf_apply: form must be 0 (automatic), 1 (VALU) or 2 (fp64 MFMA)");
   if (den && n_lib < 1) return set_error("frei_ccf_apply: n_lib must be >= 1 with den");
-  if (den && select)
-    for (int m = 0; m < n_atm; ++m)
-      if (select[m] < 0 || select[m] >= n_lib)
-        return set_error("frei_ccf_apply: select[" + std::to_string(m) + "] = " +
-                         std::to_string(select[m]) + " lies outside [0, n_lib = " +
-                         std::to_string(n_lib) + ")");
-  CtxRows cr{};
-  BrdRows br{};
-  if (brd) {
-    if (int rc = brd_kept_rows(brd, &br)) return rc;
-    if (!br.rows)
-      return set_error("frei_ccf_apply_brd: the broadener holds nothing kept (apply with keep)");
-    if (br.n_lam != c->n_lam)
-      return set_error("frei_ccf_apply_brd: the broadener's n_lam = " + std::to_string(br.n_lam) +
-                       " is not the correlator's " + std::to_string(c->n_lam));
-    if (br.n_atm != n_atm)
-      return set_error("frei_ccf_apply_brd: the broadener keeps " + std::to_string(br.n_atm) +
-                       " atmospheres, not n_atm = " + std::to_string(n_atm));
-    if (br.device != c->device)
-      return set_error("frei_ccf_apply_brd: broadener and correlator live on different devices");
-  } else if (!x) {
-    if (int rc = ctx_emergent_rows(ctx, &cr)) return rc;
-    if (cr.n_atm != n_atm)
-      return set_error("frei_ccf_apply: the context holds " + std::to_string(cr.n_atm) +
-                       " atmospheres, not n_atm = " + std::to_string(n_atm));
-    if (cr.n_lam != c->n_lam)
-      return set_error("frei_ccf_apply: the context's n_lam = " + std::to_string(cr.n_lam) +
-                       " is not the correlator's " + std::to_string(c->n_lam));
-    if (cr.device != c->device)
-      return set_error("frei_ccf_apply: context and correlator live on different devices");
-  }
+  if (den) TRY(check_select("frei_ccf_apply", select, n_atm, n_lib));
+  SpectrumRows rows;
+  TRY(spectrum_rows(x, ctx, brd, n_atm, c->n_lam, c->device, c->stream, "correlator",
+                    "frei_ccf_apply", &rows));
   int f = form;
   if (f == 0) f = c->n_exp >= kMfmaFromExposures ? 2 : 1;
   if (form_used) *form_used = f;
 
   HIP_TRY(hipSetDevice(c->device));
-  // the context's own stream where its spectra are read in place: ordered behind its work
-  hipStream_t st = (x || brd) ? c->stream : cr.stream;
+  hipStream_t st = rows.stream;
   const size_t A = (size_t)n_atm, n = (size_t)c->n_lam, V = (size_t)c->n_vel,
                E = (size_t)c->n_exp;
   const bool prepass = den || scale || offset;
   const int nc = (int)((c->n_pix + kChunk - 1) / kChunk);   // chunks: partial sums beyond one
   if ((int64_t)nc * ((c->n_exp + kET - 1) / kET) > 65535)
     return set_error("frei_ccf_apply: n_pix / 4096 * n_exp / 8 exceeds the launch grid");
-  double *u_x = nullptr, *d_den = nullptr, *d_scale = nullptr, *d_off = nullptr, *d_y = nullptr,
-         *d_sfg = nullptr, *d_sg = nullptr, *d_sgg = nullptr, *p_sfg = nullptr, *p_sg = nullptr,
-         *p_sgg = nullptr;
-  int32_t* d_sel = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int rc = 0;
-  if (x && !(rc = dalloc(&u_x, A * n))) rc = h2d(u_x, x, A * n, st);
-  if (!rc && den && !(rc = dalloc(&d_den, (size_t)n_lib * n)))
-    rc = h2d(d_den, den, (size_t)n_lib * n, st);
-  if (!rc && den && select && !(rc = dalloc(&d_sel, A))) rc = h2d(d_sel, select, A, st);
-  if (!rc && scale && !(rc = dalloc(&d_scale, A))) rc = h2d(d_scale, scale, A, st);
-  if (!rc && offset && !(rc = dalloc(&d_off, A))) rc = h2d(d_off, offset, A, st);
-  if (!rc && prepass) rc = dalloc(&d_y, A * n);
-  if (!rc && sfg) rc = dalloc(&d_sfg, A * E * V);
-  if (!rc && sg) rc = dalloc(&d_sg, A * V);
-  if (!rc && sgg) rc = dalloc(&d_sgg, A * V);
-  if (!rc && nc > 1 && sfg) rc = dalloc(&p_sfg, (size_t)nc * A * E * V);
-  if (!rc && nc > 1 && sg) rc = dalloc(&p_sg, (size_t)nc * A * V);
-  if (!rc && nc > 1 && sgg) rc = dalloc(&p_sgg, (size_t)nc * A * V);
-  if (!rc && kernel_ms) {
-    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess ||
-        hipEventRecord(ev[0], st) != hipSuccess)
-      rc = set_error("frei_ccf_apply: timing event failed");
-  }
-  if (!rc) {
-    const double* src = u_x ? u_x : brd ? br.rows : cr.rows;
-    const int64_t xs = (u_x || brd) ? (int64_t)n : cr.stride;
+  DeviceCall call(st, "cross-correlation");
+  auto result = [&](bool want, size_t cnt) { return want ? call.alloc<double>(cnt) : nullptr; };
+  const double* u_x = call.upload(x, A * n);
+  const double* d_den = call.upload(den, (size_t)n_lib * n);
+  const int32_t* d_sel = call.upload(den ? select : nullptr, A);
+  const double* d_scale = call.upload(scale, A);
+  const double* d_off = call.upload(offset, A);
+  double* d_y = result(prepass, A * n);
+  double* d_sfg = result(sfg, A * E * V);
+  double* d_sg = result(sg, A * V);
+  double* d_sgg = result(sgg, A * V);
+  double* p_sfg = result(nc > 1 && sfg, (size_t)nc * A * E * V);
+  double* p_sg = result(nc > 1 && sg, (size_t)nc * A * V);
+  double* p_sgg = result(nc > 1 && sgg, (size_t)nc * A * V);
+  call.begin(kernel_ms);
+  if (call.ok()) {
+    const double* src = u_x ? u_x : rows.rows;
+    const int64_t xs = rows.stride;
     if (prepass)
       ccf_template_kernel<<<dim3((unsigned)((n + 255) / 256), (unsigned)n_atm), 256, 0, st>>>(
           src, xs, d_den, d_sel, d_scale, d_off, c->n_lam, d_y);
@@ -638,34 +583,12 @@ static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd*
       combine(p_sg, a.g_size, d_sg);
       combine(p_sgg, a.g_size, d_sgg);
     }
-    if (hipGetLastError() != hipSuccess) rc = set_error("cross-correlation kernel launch failed");
   }
-  if (!rc && kernel_ms) {
-    float ms = 0;
-    if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
-        hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess)
-      rc = set_error("frei_ccf_apply: timing event failed");
-    else
-      *kernel_ms = ms;
-  }
-  auto d2h = [&](double* h, const double* d, size_t cnt) {
-    if (!rc && h &&
-        hipMemcpyAsync(h, d, cnt * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
-      rc = set_error("cross-correlation copy failed");
-  };
-  d2h(sfg, d_sfg, A * E * V);
-  d2h(sg, d_sg, A * V);
-  d2h(sgg, d_sgg, A * V);
-  if (hipStreamSynchronize(st) != hipSuccess && !rc)
-    rc = set_error("cross-correlation kernel failed");
-  for (auto& e : ev)
-    if (e) (void)hipEventDestroy(e);
-  for (void* p : {(void*)u_x, (void*)d_den, (void*)d_sel, (void*)d_scale, (void*)d_off,
-                  (void*)d_y, (void*)d_sfg, (void*)d_sg, (void*)d_sgg, (void*)p_sfg, (void*)p_sg,
-                  (void*)p_sgg})
-    if (p) (void)hipFree(p);
-  if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
-  return rc;
+  call.end();
+  call.download(sfg, d_sfg, A * E * V);
+  call.download(sg, d_sg, A * V);
+  call.download(sgg, d_sgg, A * V);
+  return call.finish();
 }
 
 int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const double* den,

@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "../../include/frei_hip.h"
-#include "frei_device.h"
+#include "frei_host.h"
 
 using namespace frei;
 
@@ -46,12 +46,6 @@ constexpr int kTile = 4;   // atmospheres per block
 // the feature's specification pins (tests/test_gpu_observe.py, test_both_regimes), at a measured
 // cost of 9 to 17 % for such instruments at 500k.
 constexpr double kGroupPerChannelFrom = 4.0;
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) return set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 struct ObsArgs {
   const double* x;        // row m at x + m * xs
@@ -215,18 +209,6 @@ int group_lanes(double mean_points) {
          : mean_points >= 12.0 ? 8 : 4;
 }
 
-template <typename T>
-int dalloc(T** p, size_t n) {
-  HIP_TRY(hipMalloc((void**)p, (n ? n : 1) * sizeof(T)));
-  return 0;
-}
-
-template <typename T>
-int h2d(T* d, const T* h, size_t n, hipStream_t st) {
-  HIP_TRY(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-  return 0;
-}
-
 }  // namespace
 
 // ==================================================================== C ABI
@@ -311,12 +293,7 @@ static int obs_apply_impl(frei_obs* o, frei_ctx* ctx, const double* x, frei_brd*
                      "(group per channel)");
   const bool lib = num || den;
   if (lib && n_lib < 1) return set_error("frei_obs_apply: n_lib must be >= 1 with num or den");
-  if (lib && select)
-    for (int m = 0; m < n_atm; ++m)
-      if (select[m] < 0 || select[m] >= n_lib)
-        return set_error("frei_obs_apply: select[" + std::to_string(m) + "] = " +
-                         std::to_string(select[m]) + " lies outside [0, n_lib = " +
-                         std::to_string(n_lib) + ")");
+  if (lib) TRY(check_select("frei_obs_apply", select, n_atm, n_lib));
   if (chi2) {
     if (!data || !sigma) return set_error("frei_obs_apply: chi2 requested without data or sigma");
     for (int64_t k = 0; k < o->K; ++k)
@@ -324,110 +301,51 @@ static int obs_apply_impl(frei_obs* o, frei_ctx* ctx, const double* x, frei_brd*
         return set_error("frei_obs_apply: sigma[" + std::to_string(k) +
                          "] must be > 0 (+inf removes the channel)");
   }
-  CtxRows cr{};
-  BrdRows br{};
-  if (brd) {
-    if (int rc = brd_kept_rows(brd, &br)) return rc;
-    if (!br.rows)
-      return set_error("frei_obs_apply_brd: the broadener holds nothing kept (apply with keep)");
-    if (br.n_lam != o->n_lam)
-      return set_error("frei_obs_apply_brd: the broadener's n_lam = " + std::to_string(br.n_lam) +
-                       " is not the instrument's " + std::to_string(o->n_lam));
-    if (br.n_atm != n_atm)
-      return set_error("frei_obs_apply_brd: the broadener keeps " + std::to_string(br.n_atm) +
-                       " atmospheres, not n_atm = " + std::to_string(n_atm));
-    if (br.device != o->device)
-      return set_error("frei_obs_apply_brd: broadener and instrument live on different devices");
-  } else if (!x) {
-    if (int rc = ctx_emergent_rows(ctx, &cr)) return rc;
-    if (cr.n_atm != n_atm)
-      return set_error("frei_obs_apply: the context holds " + std::to_string(cr.n_atm) +
-                       " atmospheres, not n_atm = " + std::to_string(n_atm));
-    if (cr.n_lam != o->n_lam)
-      return set_error("frei_obs_apply: the context's n_lam = " + std::to_string(cr.n_lam) +
-                       " is not the instrument's " + std::to_string(o->n_lam));
-    if (cr.device != o->device)
-      return set_error("frei_obs_apply: context and instrument live on different devices");
-  }
+  SpectrumRows src;
+  TRY(spectrum_rows(x, ctx, brd, n_atm, o->n_lam, o->device, o->stream, "instrument",
+                    "frei_obs_apply", &src));
   const double mean_points = (double)o->nnz / (double)o->K;
   int f = form;
   if (f == 0) f = mean_points > kGroupPerChannelFrom ? 2 : 1;
   if (form_used) *form_used = f;
 
   HIP_TRY(hipSetDevice(o->device));
-  // the context's own stream where its spectra are read in place: ordered behind its work
-  hipStream_t st = (x || brd) ? o->stream : cr.stream;
+  hipStream_t st = src.stream;
   const size_t A = (size_t)n_atm, n = (size_t)o->n_lam, K = (size_t)o->K;
-  double *u_x = nullptr, *d_num = nullptr, *d_den = nullptr, *d_scale = nullptr,
-         *d_data = nullptr, *d_sigma = nullptr, *d_obs = nullptr, *d_chi2 = nullptr;
-  int32_t* d_sel = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int rc = 0;
-  if (x && !(rc = dalloc(&u_x, A * n))) rc = h2d(u_x, x, A * n, st);
-  if (!rc && num && !(rc = dalloc(&d_num, (size_t)n_lib * n)))
-    rc = h2d(d_num, num, (size_t)n_lib * n, st);
-  if (!rc && den && !(rc = dalloc(&d_den, (size_t)n_lib * n)))
-    rc = h2d(d_den, den, (size_t)n_lib * n, st);
-  if (!rc && lib && select && !(rc = dalloc(&d_sel, A))) rc = h2d(d_sel, select, A, st);
-  if (!rc && scale && !(rc = dalloc(&d_scale, A))) rc = h2d(d_scale, scale, A, st);
-  if (!rc) rc = dalloc(&d_obs, A * K);
-  if (!rc && chi2) {
-    if (!(rc = dalloc(&d_data, K))) rc = h2d(d_data, data, K, st);
-    if (!rc && !(rc = dalloc(&d_sigma, K))) rc = h2d(d_sigma, sigma, K, st);
-    if (!rc) rc = dalloc(&d_chi2, A);
-  }
-  if (!rc && kernel_ms) {
-    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess ||
-        hipEventRecord(ev[0], st) != hipSuccess)
-      rc = set_error("frei_obs_apply: timing event failed");
-  }
-  if (!rc) {
-    ObsArgs a;
-    a.x = u_x ? u_x : brd ? br.rows : cr.rows;
-    a.xs = (u_x || brd) ? (int64_t)n : cr.stride;
-    a.num = d_num;
-    a.den = d_den;
-    a.select = d_sel;
-    a.scale = d_scale;
-    a.first = o->d_plan;
-    a.count = o->d_plan + K;
-    a.off = o->d_plan + 2 * K;
-    a.w = o->d_w;
-    a.K = o->K;
-    a.n = o->n_lam;
-    a.n_atm = n_atm;
-    a.obs = d_obs;
+  DeviceCall call(st, "observation");
+  ObsArgs a;
+  const double* u_x = call.upload(x, A * n);
+  a.x = u_x ? u_x : src.rows;
+  a.xs = src.stride;
+  a.num = call.upload(num, (size_t)n_lib * n);
+  a.den = call.upload(den, (size_t)n_lib * n);
+  a.select = call.upload(lib ? select : nullptr, A);
+  a.scale = call.upload(scale, A);
+  a.first = o->d_plan;
+  a.count = o->d_plan + K;
+  a.off = o->d_plan + 2 * K;
+  a.w = o->d_w;
+  a.K = o->K;
+  a.n = o->n_lam;
+  a.n_atm = n_atm;
+  a.obs = call.alloc<double>(A * K);
+  const double* d_data = call.upload(chi2 ? data : nullptr, K);
+  const double* d_sigma = call.upload(chi2 ? sigma : nullptr, K);
+  double* d_chi2 = chi2 ? call.alloc<double>(A) : nullptr;
+  call.begin(kernel_ms);
+  if (call.ok()) {
     const int G = group_lanes(mean_points);
     if (num && den) launch_form<true, true>(f, G, a, st);
     else if (num) launch_form<true, false>(f, G, a, st);
     else if (den) launch_form<false, true>(f, G, a, st);
     else launch_form<false, false>(f, G, a, st);
     if (chi2)
-      obs_chi2_kernel<<<dim3((unsigned)n_atm), 64, 0, st>>>(d_obs, d_data, d_sigma, o->K, d_chi2);
-    if (hipGetLastError() != hipSuccess) rc = set_error("observation kernel launch failed");
+      obs_chi2_kernel<<<dim3((unsigned)n_atm), 64, 0, st>>>(a.obs, d_data, d_sigma, o->K, d_chi2);
   }
-  if (!rc && kernel_ms) {
-    float ms = 0;
-    if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
-        hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess)
-      rc = set_error("frei_obs_apply: timing event failed");
-    else
-      *kernel_ms = ms;
-  }
-  if (!rc && hipMemcpyAsync(obs, d_obs, A * K * sizeof(double), hipMemcpyDeviceToHost, st) !=
-                 hipSuccess)
-    rc = set_error("observation copy failed");
-  if (!rc && chi2 &&
-      hipMemcpyAsync(chi2, d_chi2, A * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)
-    rc = set_error("observation copy failed");
-  if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_error("observation kernel failed");
-  for (auto& e : ev)
-    if (e) (void)hipEventDestroy(e);
-  for (void* p : {(void*)u_x, (void*)d_num, (void*)d_den, (void*)d_sel, (void*)d_scale,
-                  (void*)d_data, (void*)d_sigma, (void*)d_obs, (void*)d_chi2})
-    if (p) (void)hipFree(p);
-  if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
-  return rc;
+  call.end();
+  call.download(obs, a.obs, A * K);
+  call.download(chi2, d_chi2, A);
+  return call.finish();
 }
 
 int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const double* num,

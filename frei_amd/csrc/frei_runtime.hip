@@ -17,7 +17,7 @@
 #include <vector>
 
 #include "../../include/frei_hip.h"
-#include "frei_device.h"
+#include "frei_host.h"
 
 using namespace frei;
 
@@ -37,19 +37,6 @@ int set_error(const std::string& msg) { return fail(msg); }
 }  // namespace frei
 
 namespace {
-
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t _e = (expr);                                                        \
-    if (_e != hipSuccess)                                                          \
-      return fail(std::string(#expr) + ": " + hipGetErrorString(_e));              \
-  } while (0)
-
-#define TRY(expr)                 \
-  do {                            \
-    int _r = (expr);              \
-    if (_r != 0) return _r;       \
-  } while (0)
 
 // ---------------------------------------------------------------- RCCL (dlopen)
 struct Rccl {
@@ -309,34 +296,11 @@ int set_device(frei_ctx* c) {
   return 0;
 }
 
+// A setup or per-run upload (never inside the T-P loop) that waits for the copy: the sources are
+// often temporaries (pageable, freed at the caller's scope exit).
 template <typename T>
-int dalloc(T** p, size_t n) {
-  if (n == 0) n = 1;
-  HIP_TRY(hipMalloc((void**)p, n * sizeof(T)));
-  // FREI_ALLOC_FILL (diagnostic): fill every new device buffer with a byte value, so a read of
-  // memory the engine never wrote shows up as changed results
-  static const int fill = [] {
-    const char* e = getenv("FREI_ALLOC_FILL");
-    return e ? atoi(e) : -1;
-  }();
-  if (fill >= 0) {   // (the null-stream memset must finish before the context's stream uses p)
-    HIP_TRY(hipMemset((void*)*p, fill, n * sizeof(T)));
-    HIP_TRY(hipDeviceSynchronize());
-  }
-  return 0;
-}
-
-template <typename T>
-void dfree(T*& p) {
-  if (p) (void)hipFree((void*)p);
-  p = nullptr;
-}
-
-template <typename T>
-int h2d(T* d, const T* h, size_t n, hipStream_t st) {
-  HIP_TRY(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-  // the sources are often temporaries (pageable, freed at the caller's scope exit): wait for
-  // the copy (setup and per-run uploads only, never inside the T-P loop)
+int h2d_wait(T* d, const T* h, size_t n, hipStream_t st) {
+  TRY(h2d(d, h, n, st));
   HIP_TRY(hipStreamSynchronize(st));
   return 0;
 }
@@ -483,11 +447,11 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   if (!c->d_ones) {
     std::vector<double> ones(nL, 1.0);
     TRY(dalloc(&c->d_ones, nL));
-    TRY(h2d(c->d_ones, ones.data(), nL, c->stream));
+    TRY(h2d_wait(c->d_ones, ones.data(), nL, c->stream));
   }
   dfree(c->d_prow);
   TRY(dalloc(&c->d_prow, nL));
-  TRY(h2d(c->d_prow, prow.data(), nL, c->stream));
+  TRY(h2d_wait(c->d_prow, prow.data(), nL, c->stream));
   const double* tabs[kMaxFastS];
   for (int s = 0; s < S; ++s) tabs[s] = c->sp[s].d_tab;
   // lazy K3: the sweeps that read this table take two wavelengths per lane (the form run_sweep
@@ -507,7 +471,7 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
     SpecMeta m = c->smeta[0];
     m.tab = c->d_eff;
     if (!c->d_smeta_eff) TRY(dalloc(&c->d_smeta_eff, 1));
-    TRY(h2d(c->d_smeta_eff, &m, 1, c->stream));
+    TRY(h2d_wait(c->d_smeta_eff, &m, 1, c->stream));
     return 0;
   }
   hipEvent_t k0 = nullptr, k1 = nullptr;   // the contraction kernel alone (frei_contract_timing)
@@ -544,7 +508,7 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   SpecMeta m = c->smeta[0];
   m.tab = c->d_eff;
   if (!c->d_smeta_eff) TRY(dalloc(&c->d_smeta_eff, 1));
-  TRY(h2d(c->d_smeta_eff, &m, 1, c->stream));
+  TRY(h2d_wait(c->d_smeta_eff, &m, 1, c->stream));
   return 0;
 }
 
@@ -678,12 +642,12 @@ int build_meta(frei_ctx* c) {
   TRY(dalloc(&c->d_pmeta, (size_t)S * nL));
   TRY(dalloc(&c->d_tnodes, c->tnodes.size()));
   TRY(dalloc(&c->d_tperm, c->tperm.size()));
-  TRY(h2d(c->d_smeta, c->smeta.data(), S, c->stream));
-  TRY(h2d(c->d_pmeta, c->pmeta.data(), (size_t)S * nL, c->stream));
-  TRY(h2d(c->d_tnodes, c->tnodes.data(), c->tnodes.size(), c->stream));
-  TRY(h2d(c->d_tperm, c->tperm.data(), c->tperm.size(), c->stream));
+  TRY(h2d_wait(c->d_smeta, c->smeta.data(), S, c->stream));
+  TRY(h2d_wait(c->d_pmeta, c->pmeta.data(), (size_t)S * nL, c->stream));
+  TRY(h2d_wait(c->d_tnodes, c->tnodes.data(), c->tnodes.size(), c->stream));
+  TRY(h2d_wait(c->d_tperm, c->tperm.data(), c->tperm.size(), c->stream));
   if (c->mmr.size() != (size_t)S * nL * c->n_atm) return fail("frei_set_mmr must be called");
-  TRY(h2d(c->d_mmr, c->mmr.data(), (size_t)S * nL * c->n_atm, c->stream));
+  TRY(h2d_wait(c->d_mmr, c->mmr.data(), (size_t)S * nL * c->n_atm, c->stream));
   lap(1);
   TRY(build_contracted(c, fast && shared, lap));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -945,7 +909,7 @@ int complete_contraction(frei_ctx* c) {
   std::vector<int32_t> ones((size_t)q0.n_p * q0.n_T, 0);
   for (int l = 0; l < c->nL; ++l)
     for (int t = 0; t < q0.n_T; ++t) ones[(size_t)prow[l] * q0.n_T + t] = 1;
-  TRY(h2d(c->d_kvalid, ones.data(), ones.size(), c->stream));
+  TRY(h2d_wait(c->d_kvalid, ones.data(), ones.size(), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));   // (the host vector)
   c->eff_complete = true;
   return 0;
@@ -1590,20 +1554,20 @@ int frei_set_grid(frei_ctx* c, const double* c1, const double* lk, const double*
   c->m_bar = m_bar;
   if (c->n_atm > 1) {  // default gravity of every atmosphere (frei_set_gravity overrides)
     std::vector<double> gv(c->n_atm, g);
-    TRY(h2d(c->d_g, gv.data(), gv.size(), c->stream));
+    TRY(h2d_wait(c->d_g, gv.data(), gv.size(), c->stream));
   }
-  TRY(h2d(c->d_c1, c1, n, c->stream));
+  TRY(h2d_wait(c->d_c1, c1, n, c->stream));
   {   // the Planck exponent's per-wavelength factor hc / (lam k_B) (kernels: times 1 / T)
     std::vector<double> hcl(n);
     for (int64_t j = 0; j < n; ++j) hcl[j] = kHC / lk[j];
-    TRY(h2d(c->d_hcl, hcl.data(), n, c->stream));
+    TRY(h2d_wait(c->d_hcl, hcl.data(), n, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));   // hcl is a temporary
   }
-  TRY(h2d(c->d_sig, sigma, n, c->stream));
-  TRY(h2d(c->d_ftoa, f_toa, n, c->stream));
+  TRY(h2d_wait(c->d_sig, sigma, n, c->stream));
+  TRY(h2d_wait(c->d_ftoa, f_toa, n, c->stream));
   c->ftoa_per_atm = false;   // one F_TOA for every atmosphere again
-  TRY(h2d(c->d_wtr, trapz_w, n, c->stream));
-  TRY(h2d(c->d_p, c->p.data(), c->nL, c->stream));
+  TRY(h2d_wait(c->d_wtr, trapz_w, n, c->stream));
+  TRY(h2d_wait(c->d_p, c->p.data(), c->nL, c->stream));
   launch_log_ratio(c->d_p, c->p_top2, c->nL, c->d_lnp, c->stream);
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->grid_set = true;
@@ -1705,9 +1669,9 @@ int frei_set_table_separable(frei_ctx* c, int s, const double* base, const doubl
   TRY(dalloc(&d_base, c->nlam));
   TRY(dalloc(&d_fp, n_p));
   TRY(dalloc(&d_fT, n_T));
-  TRY(h2d(d_base, base, c->nlam, c->stream));
-  TRY(h2d(d_fp, fp, n_p, c->stream));
-  TRY(h2d(d_fT, fT, n_T, c->stream));
+  TRY(h2d_wait(d_base, base, c->nlam, c->stream));
+  TRY(h2d_wait(d_fp, fp, n_p, c->stream));
+  TRY(h2d_wait(d_fT, fT, n_T, c->stream));
   launch_gen_table(c->sp[s].d_tab, d_base, d_fp, d_fT, n_p, n_T, c->nlam, c->sp[s].stride, lo,
                    hi, c->stream);
   HIP_TRY(hipGetLastError());
@@ -1762,7 +1726,7 @@ int frei_set_ftoa_batch(frei_ctx* c, const double* f_toa) {
   const size_t n = (size_t)c->nlam * c->n_atm;
   double* d = nullptr;
   TRY(dalloc(&d, n));
-  if (h2d(d, f_toa, n, c->stream) || hipStreamSynchronize(c->stream) != hipSuccess) {
+  if (h2d_wait(d, f_toa, n, c->stream) || hipStreamSynchronize(c->stream) != hipSuccess) {
     dfree(d);
     return fail("F_TOA upload failed");
   }
@@ -1803,15 +1767,15 @@ static int set_chem_tables(frei_ctx* c, const double* values, int n_tab, const i
   TRY(dalloc(&c->d_chem_T, n_T));
   TRY(dalloc(&c->d_chem_pj, nL));
   TRY(dalloc(&c->d_chem_pz, nL));
-  TRY(h2d(c->d_chem_tab, c->chem_tab.data(), nv, c->stream));
-  TRY(h2d(c->d_chem_T, c->chem_T.data(), n_T, c->stream));
-  TRY(h2d(c->d_chem_pj, pj.data(), nL, c->stream));
-  TRY(h2d(c->d_chem_pz, pz.data(), nL, c->stream));
+  TRY(h2d_wait(c->d_chem_tab, c->chem_tab.data(), nv, c->stream));
+  TRY(h2d_wait(c->d_chem_T, c->chem_T.data(), n_T, c->stream));
+  TRY(h2d_wait(c->d_chem_pj, pj.data(), nL, c->stream));
+  TRY(h2d_wait(c->d_chem_pz, pz.data(), nL, c->stream));
   c->chem_atm.clear();
   if (atm_tab) {
     c->chem_atm.assign(atm_tab, atm_tab + c->n_atm);
     TRY(dalloc(&c->d_chem_atm, c->n_atm));
-    TRY(h2d(c->d_chem_atm, c->chem_atm.data(), c->n_atm, c->stream));
+    TRY(h2d_wait(c->d_chem_atm, c->chem_atm.data(), c->n_atm, c->stream));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
   c->chem_ntab = n_tab;
@@ -1865,7 +1829,7 @@ int frei_set_gravity(frei_ctx* c, const double* g) {
   for (int m = 0; m < c->n_atm; ++m)
     if (!(g[m] > 0)) return fail("g must be positive");
   TRY(set_device(c));
-  TRY(h2d(c->d_g, g, c->n_atm, c->stream));
+  TRY(h2d_wait(c->d_g, g, c->n_atm, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1874,8 +1838,8 @@ int frei_set_fluxes(frei_ctx* c, const double* up, const double* down) {
   if (!c) return fail("null argument");
   TRY(set_device(c));
   const size_t F = (size_t)c->nL * c->nlam * c->n_atm;
-  if (up) TRY(h2d(c->d_Fu, up, F, c->stream));
-  if (down) TRY(h2d(c->d_Fd, down, F, c->stream));
+  if (up) TRY(h2d_wait(c->d_Fu, up, F, c->stream));
+  if (down) TRY(h2d_wait(c->d_Fd, down, F, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1907,7 +1871,7 @@ int frei_set_temperatures(frei_ctx* c, const double* T) {
     if (!(T[l] > 0)) return fail("temperatures must be positive");
   TRY(set_device(c));
   home_temperatures(c);
-  TRY(h2d(c->d_T, T, n, c->stream));
+  TRY(h2d_wait(c->d_T, T, n, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -1971,7 +1935,7 @@ int frei_state_init(frei_ctx* c, const double* T_init) {
   TRY(build_meta(c));
   c->has_pend = false;   // an update deferred by an interrupted run must not land on the new T
   home_temperatures(c);
-  TRY(h2d(c->d_T, T_init, (size_t)c->nL * c->n_atm, c->stream));
+  TRY(h2d_wait(c->d_T, T_init, (size_t)c->nL * c->n_atm, c->stream));
   const size_t F = (size_t)c->nL * c->nlam * c->n_atm;
   HIP_TRY(hipMemsetAsync(c->d_Fu, 0, F * sizeof(double), c->stream));  // core.py:265-266
   HIP_TRY(hipMemsetAsync(c->d_Fd, 0, F * sizeof(double), c->stream));
@@ -2302,7 +2266,7 @@ int frei_kappa(frei_ctx* c, double T, double p, double* k, double* sigma) {
   double* d_k = nullptr;
   TRY(dalloc(&d_terms, c->S));
   TRY(dalloc(&d_k, c->nlam));
-  TRY(h2d(d_terms, terms.data(), c->S, c->stream));
+  TRY(h2d_wait(d_terms, terms.data(), c->S, c->stream));
   launch_kappa(c->nlam, d_terms, c->S, c->d_sig, d_k, c->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2330,7 +2294,7 @@ int frei_propagate_fluxes(int device, int64_t n, const double* c1, const double*
   if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess)
     return fail("hipStreamCreate failed");
   for (int i = 0; i < n_in + 2 && !rc; ++i) rc = dalloc(&d[i], n);
-  for (int i = 0; i < n_in && !rc; ++i) rc = h2d(d[i], in[i], n, st);
+  for (int i = 0; i < n_in && !rc; ++i) rc = h2d_wait(d[i], in[i], n, st);
   if (!rc) {
     launch_propagate(n, d[0], d[1], d[2], d[3], T_1, T_2, d[4], d[5], g_0 ? d[6] : nullptr,
                      d[n_in], d[n_in + 1], st);
@@ -2448,7 +2412,7 @@ int frei_comm_p2p_open(frei_ctx* c, const void* handles) {
     ptr[r] = static_cast<double*>(p);
   }
   TRY(dalloc(&c->d_peers, R));
-  TRY(h2d(c->d_peers, ptr.data(), R, c->stream));
+  TRY(h2d_wait(c->d_peers, ptr.data(), R, c->stream));
   TRY(dalloc(&c->d_comm_err, 1));
   TRY(dalloc(&c->d_wait_ticks, 1));
   HIP_TRY(hipMemsetAsync(c->d_comm_err, 0, sizeof(int), c->stream));
@@ -2475,101 +2439,56 @@ int frei_comm_p2p_open(frei_ctx* c, const void* handles) {
   return check_comm(c);
 }
 
-// dtaus for post-processing: the caller's host array (uploaded) or the device copy.
-static int post_dtaus(frei_ctx* c, const double* h, double** tmp, const double** d) {
-  *tmp = nullptr;
-  if (c->n_atm > 1) return fail("post-processing is per atmosphere: use a single context");
-  if (h) {
-    const size_t n = (size_t)c->nL * c->nlam;
-    TRY(dalloc(tmp, n));
-    TRY(h2d(*tmp, h, n, c->stream));
-    *d = *tmp;
-    return 0;
-  }
-  if (!c->dtaus_valid || !c->d_dtaus) return fail("no device dtaus: run frei_run first or pass dtaus");
-  *d = c->d_dtaus;
-  return 0;
+// The dtaus a post-processing call reads when the caller passes none: the last run's, kept on
+// the device (a batched run's with keep_dtaus).
+static int need_device_dtaus(frei_ctx* c, bool batch) {
+  if (c->d_dtaus && (batch ? c->dtaus_batch_valid : c->dtaus_valid)) return 0;
+  return fail(batch ? "no device dtaus: run frei_run_batch_ex with keep_dtaus first, or pass dtaus"
+                    : "no device dtaus: run frei_run first or pass dtaus");
 }
 
-// HIP events around a post-processing call's kernels (frei_post_timing): begin() before the
-// launches, end() after them, read() once the stream is synchronised.
-struct PostTimer {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  void begin(hipStream_t st) {
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipEventRecord(e0, st) != hipSuccess)
-      drop();
-  }
-  void end(hipStream_t st) {
-    if (e0 && hipEventRecord(e1, st) != hipSuccess) drop();
-  }
-  void read(frei_ctx* c) {
-    float ms = 0.f;
-    c->post_ms = (e0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) ? (double)ms : 0.0;
-    drop();
-  }
-  void drop() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    e0 = e1 = nullptr;
-  }
-};
+// dtaus for a single context's post-processing: the caller's host array or frei_run's.
+static int post_dtaus(frei_ctx* c, const double* h) {
+  if (c->n_atm > 1) return fail("post-processing is per atmosphere: use a single context");
+  return h ? 0 : need_device_dtaus(c, false);
+}
 
+// The post-processing calls below time their kernels into c->post_ms (frei_post_timing).
 int frei_milne_pressure(frei_ctx* c, const double* dtaus, const double* p_bar,
                         double* p_milne) {
   if (!ready(c) || !p_bar || !p_milne) return fail("context not ready or null argument");
   TRY(set_device(c));
-  double *tmp = nullptr, *d_fp = nullptr, *d_out = nullptr;
-  const double* d_dt = nullptr;
-  PostTimer tm;
-  int rc = post_dtaus(c, dtaus, &tmp, &d_dt);
-  if (!rc) rc = dalloc(&d_fp, c->nL);
-  if (!rc) rc = dalloc(&d_out, c->nlam);
-  if (!rc) rc = h2d(d_fp, p_bar, c->nL, c->stream);
-  if (!rc) {
-    tm.begin(c->stream);
-    launch_milne(d_dt, c->nL, c->nlam, d_fp, d_out, c->stream);
-    if (hipGetLastError() != hipSuccess) rc = fail("milne kernel launch failed");
-    tm.end(c->stream);
-  }
-  if (!rc && hipMemcpyAsync(p_milne, d_out, c->nlam * sizeof(double), hipMemcpyDeviceToHost,
-                            c->stream) != hipSuccess)
-    rc = fail("milne copy failed");
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("milne kernel failed");
-  tm.read(c);
-  dfree(tmp), dfree(d_fp), dfree(d_out);
-  return rc;
+  TRY(post_dtaus(c, dtaus));
+  DeviceCall call(c->stream, "milne");
+  const double* u_dt = call.upload(dtaus, (size_t)c->nL * c->nlam);
+  const double* d_fp = call.upload(p_bar, c->nL);
+  double* d_out = call.alloc<double>(c->nlam);
+  call.begin(&c->post_ms);
+  if (call.ok()) launch_milne(u_dt ? u_dt : c->d_dtaus, c->nL, c->nlam, d_fp, d_out, c->stream);
+  call.end();
+  call.download(p_milne, d_out, c->nlam);
+  return call.finish();
 }
 
 int frei_contribution(frei_ctx* c, const double* dtaus, const double* nu, const double* ratio,
                       const double* T, double hcperk, double* cf) {
   if (!ready(c) || !nu || !ratio || !T || !cf) return fail("context not ready or null argument");
   TRY(set_device(c));
-  double *tmp = nullptr, *d_nu = nullptr, *d_ratio = nullptr, *d_T = nullptr, *d_cf = nullptr;
-  const double* d_dt = nullptr;
+  TRY(post_dtaus(c, dtaus));
   const size_t n = (size_t)c->nL * c->nlam;
-  int rc = post_dtaus(c, dtaus, &tmp, &d_dt);
-  if (!rc) rc = dalloc(&d_nu, c->nlam);
-  if (!rc) rc = dalloc(&d_ratio, c->nL);
-  if (!rc) rc = dalloc(&d_T, c->nL);
-  if (!rc) rc = dalloc(&d_cf, n);
-  if (!rc) rc = h2d(d_nu, nu, c->nlam, c->stream);
-  if (!rc) rc = h2d(d_ratio, ratio, c->nL, c->stream);
-  if (!rc) rc = h2d(d_T, T, c->nL, c->stream);
-  PostTimer tm;
-  if (!rc) {
-    tm.begin(c->stream);
-    launch_contribution(d_dt, c->nL, c->nlam, d_nu, d_ratio, d_T, hcperk, d_cf, c->stream);
-    if (hipGetLastError() != hipSuccess) rc = fail("contribution kernel launch failed");
-    tm.end(c->stream);
-  }
-  if (!rc && hipMemcpyAsync(cf, d_cf, n * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
-                 hipSuccess)
-    rc = fail("contribution copy failed");
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("contribution kernel failed");
-  tm.read(c);
-  dfree(tmp), dfree(d_nu), dfree(d_ratio), dfree(d_T), dfree(d_cf);
-  return rc;
+  DeviceCall call(c->stream, "contribution");
+  const double* u_dt = call.upload(dtaus, n);
+  const double* d_nu = call.upload(nu, c->nlam);
+  const double* d_ratio = call.upload(ratio, c->nL);
+  const double* d_T = call.upload(T, c->nL);
+  double* d_cf = call.alloc<double>(n);
+  call.begin(&c->post_ms);
+  if (call.ok())
+    launch_contribution(u_dt ? u_dt : c->d_dtaus, c->nL, c->nlam, d_nu, d_ratio, d_T, hcperk, d_cf,
+                        c->stream);
+  call.end();
+  call.download(cf, d_cf, n);
+  return call.finish();
 }
 
 int frei_get_dtaus_batch(frei_ctx* c, int atm_lo, int n, double* out) {
@@ -2602,54 +2521,32 @@ int frei_post_batch(frei_ctx* c, const double* dtaus, const double* spectra, con
   TRY(set_device(c));
   const size_t A = c->n_atm, nL = c->nL, n = c->nlam, per = nL * n;
   const int nb = post_batch_blocks(c->nlam);
-  double *u_dt = nullptr, *u_sp = nullptr, *u_T = nullptr, *d_fp = nullptr, *d_lam = nullptr,
-         *d_nu = nullptr, *d_ratio = nullptr, *d_pm = nullptr, *d_cf = nullptr,
-         *d_part = nullptr, *d_sums = nullptr;
-  PostTimer tm;
-  int rc = 0;
-  if (dtaus && !(rc = dalloc(&u_dt, A * per))) rc = h2d(u_dt, dtaus, A * per, c->stream);
-  if (!rc && spectra && !(rc = dalloc(&u_sp, A * n))) rc = h2d(u_sp, spectra, A * n, c->stream);
-  if (!rc && cf && T && !(rc = dalloc(&u_T, A * nL))) rc = h2d(u_T, T, A * nL, c->stream);
-  if (!rc) rc = dalloc(&d_fp, nL);
-  if (!rc) rc = dalloc(&d_lam, n);
-  if (!rc) rc = dalloc(&d_part, A * 3 * (size_t)nb);
-  if (!rc) rc = dalloc(&d_sums, A * 3);
-  if (!rc && p_milne) rc = dalloc(&d_pm, A * n);
-  if (!rc && cf) {
-    rc = dalloc(&d_nu, n);
-    if (!rc) rc = dalloc(&d_ratio, nL);
-    if (!rc) rc = dalloc(&d_cf, A * per);
-    if (!rc) rc = h2d(d_nu, nu, n, c->stream);
-    if (!rc) rc = h2d(d_ratio, ratio, nL, c->stream);
-  }
-  if (!rc) rc = h2d(d_fp, p_bar, nL, c->stream);
-  if (!rc) rc = h2d(d_lam, lam_cm, n, c->stream);
-  if (!rc) {
+  DeviceCall call(c->stream, "post-processing");
+  const double* u_dt = call.upload(dtaus, A * per);
+  const double* u_sp = call.upload(spectra, A * n);
+  const double* u_T = call.upload(cf ? T : nullptr, A * nL);
+  const double* d_nu = call.upload(cf ? nu : nullptr, n);
+  const double* d_ratio = call.upload(cf ? ratio : nullptr, nL);
+  const double* d_fp = call.upload(p_bar, nL);
+  const double* d_lam = call.upload(lam_cm, n);
+  double* d_part = call.alloc<double>(A * 3 * (size_t)nb);
+  double* d_sums = call.alloc<double>(A * 3);
+  double* d_pm = p_milne ? call.alloc<double>(A * n) : nullptr;
+  double* d_cf = cf ? call.alloc<double>(A * per) : nullptr;
+  call.begin(&c->post_ms);
+  if (call.ok()) {
     // the emergent row F_up[n_layers - 1] of every atmosphere, in place in the flux state
     const double* F_top = u_sp ? u_sp : c->d_Fu + (nL - 1) * n;
     const int64_t f_stride = u_sp ? (int64_t)n : (int64_t)per;
-    tm.begin(c->stream);
     launch_post_batch(u_dt ? u_dt : c->d_dtaus, F_top, f_stride, u_T ? u_T : c->d_T, d_fp, d_lam,
                       c->d_wtr, d_nu, d_ratio, hcperk, c->nL, c->nlam, c->n_atm, d_pm, d_cf,
                       d_part, d_sums, c->stream);
-    if (hipGetLastError() != hipSuccess) rc = fail("post-processing kernel launch failed");
-    tm.end(c->stream);
   }
-  auto d2h = [&](double* h, const double* d, size_t cnt) {
-    if (!rc && hipMemcpyAsync(h, d, cnt * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
-                   hipSuccess)
-      rc = fail("post-processing copy failed");
-  };
-  d2h(sums, d_sums, A * 3);
-  if (p_milne) d2h(p_milne, d_pm, A * n);
-  if (cf) d2h(cf, d_cf, A * per);
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc)
-    rc = fail("post-processing kernel failed");
-  tm.read(c);
-  dfree(u_dt), dfree(u_sp), dfree(u_T), dfree(d_fp), dfree(d_lam), dfree(d_nu), dfree(d_ratio),
-      dfree(d_pm), dfree(d_cf), dfree(d_part), dfree(d_sums);
-  if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
-  return rc;
+  call.end();
+  call.download(sums, d_sums, A * 3);
+  call.download(p_milne, d_pm, A * n);
+  call.download(cf, d_cf, A * per);
+  return call.finish();
 }
 
 int frei_transit(frei_ctx* c, const double* dtaus, const double* radii, double r_star,
@@ -2662,44 +2559,26 @@ int frei_transit(frei_ctx* c, const double* dtaus, const double* radii, double r
       if (!(radii[m * nL + k + 1] > radii[m * nL + k]))
         return fail("frei_transit: radii must be strictly ascending (atmosphere " +
                     std::to_string(m) + ", level " + std::to_string(k + 1) + ")");
-  if (!dtaus && !(c->d_dtaus && (c->batch_api ? c->dtaus_batch_valid : c->dtaus_valid)))
-    return fail(c->batch_api
-                    ? "no device dtaus: run frei_run_batch_ex with keep_dtaus first, or pass dtaus"
-                    : "no device dtaus: run frei_run first or pass dtaus");
+  if (!dtaus) TRY(need_device_dtaus(c, c->batch_api));
   TRY(set_device(c));
   // chord weights, once per call and atmosphere (wave-uniform in the kernel)
   const size_t nw = (size_t)transit_weight_count(c->nL);
   std::vector<double> w(A * nw);
   for (size_t m = 0; m < A; ++m) transit_build_weights(radii + m * nL, c->nL, w.data() + m * nw);
-  double *u_dt = nullptr, *d_r = nullptr, *d_w = nullptr, *d_depth = nullptr, *d_tau = nullptr;
-  PostTimer tm;
-  int rc = 0;
-  if (dtaus && !(rc = dalloc(&u_dt, A * per))) rc = h2d(u_dt, dtaus, A * per, c->stream);
-  if (!rc) rc = dalloc(&d_r, A * nL);
-  if (!rc) rc = dalloc(&d_w, A * nw);
-  if (!rc) rc = dalloc(&d_depth, A * n);
-  if (!rc && tau_slant) rc = dalloc(&d_tau, A * (nL - 1) * n);
-  if (!rc) rc = h2d(d_r, radii, A * nL, c->stream);
-  if (!rc) rc = h2d(d_w, w.data(), A * nw, c->stream);
-  if (!rc) {
-    tm.begin(c->stream);
+  DeviceCall call(c->stream, "transit");
+  const double* u_dt = call.upload(dtaus, A * per);
+  const double* d_r = call.upload(radii, A * nL);
+  const double* d_w = call.upload(w.data(), A * nw);
+  double* d_depth = call.alloc<double>(A * n);
+  double* d_tau = tau_slant ? call.alloc<double>(A * (nL - 1) * n) : nullptr;
+  call.begin(&c->post_ms);
+  if (call.ok())
     launch_transit(u_dt ? u_dt : c->d_dtaus, d_r, d_w, (int64_t)nw, r_star, c->nL, c->nlam,
                    c->n_atm, d_depth, d_tau, c->stream);
-    if (hipGetLastError() != hipSuccess) rc = fail("transit kernel launch failed");
-    tm.end(c->stream);
-  }
-  auto d2h = [&](double* h, const double* d, size_t cnt) {
-    if (!rc && hipMemcpyAsync(h, d, cnt * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
-                   hipSuccess)
-      rc = fail("transit copy failed");
-  };
-  d2h(depth, d_depth, A * n);
-  if (tau_slant) d2h(tau_slant, d_tau, A * (nL - 1) * n);
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("transit kernel failed");
-  tm.read(c);
-  dfree(u_dt), dfree(d_r), dfree(d_w), dfree(d_depth), dfree(d_tau);
-  if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
-  return rc;
+  call.end();
+  call.download(depth, d_depth, A * n);
+  call.download(tau_slant, d_tau, A * (nL - 1) * n);
+  return call.finish();
 }
 
 int frei_emergent(frei_ctx* c, const double* dtaus, const double* T, const double* mu,
@@ -2733,44 +2612,23 @@ int frei_emergent(frei_ctx* c, const double* dtaus, const double* T, const doubl
     }
     iT[m * (nL + 1) + nL] = iT[m * (nL + 1) + nL - 1];
   }
-  if (!dtaus && !(c->d_dtaus && (c->batch_api ? c->dtaus_batch_valid : c->dtaus_valid)))
-    return fail(c->batch_api
-                    ? "no device dtaus: run frei_run_batch_ex with keep_dtaus first, or pass dtaus"
-                    : "no device dtaus: run frei_run first or pass dtaus");
+  if (!dtaus) TRY(need_device_dtaus(c, c->batch_api));
   TRY(set_device(c));
-  double *u_dt = nullptr, *d_iT = nullptr, *d_imu = nullptr, *d_ck = nullptr, *d_int = nullptr,
-         *d_flux = nullptr;
-  PostTimer tm;
-  int rc = 0;
-  if (dtaus && !(rc = dalloc(&u_dt, A * per))) rc = h2d(u_dt, dtaus, A * per, c->stream);
-  if (!rc) rc = dalloc(&d_iT, iT.size());
-  if (!rc) rc = dalloc(&d_imu, K);
-  if (!rc && flux) rc = dalloc(&d_ck, K);
-  if (!rc && intensity) rc = dalloc(&d_int, A * K * n);
-  if (!rc && flux) rc = dalloc(&d_flux, A * n);
-  if (!rc) rc = h2d(d_iT, iT.data(), iT.size(), c->stream);
-  if (!rc) rc = h2d(d_imu, imu.data(), K, c->stream);
-  if (!rc && flux) rc = h2d(d_ck, ck.data(), K, c->stream);
-  if (!rc) {
-    tm.begin(c->stream);
+  DeviceCall call(c->stream, "emergent");
+  const double* u_dt = call.upload(dtaus, A * per);
+  const double* d_iT = call.upload(iT.data(), iT.size());
+  const double* d_imu = call.upload(imu.data(), K);
+  const double* d_ck = call.upload(flux ? ck.data() : nullptr, K);
+  double* d_int = intensity ? call.alloc<double>(A * K * n) : nullptr;
+  double* d_flux = flux ? call.alloc<double>(A * n) : nullptr;
+  call.begin(&c->post_ms);
+  if (call.ok())
     launch_emergent(u_dt ? u_dt : c->d_dtaus, c->d_c1, c->d_hcl, d_iT, d_imu, d_ck, n_mu, c->nL,
                     c->nlam, c->n_atm, d_int, d_flux, c->stream);
-    if (hipGetLastError() != hipSuccess) rc = fail("emergent kernel launch failed");
-    tm.end(c->stream);
-  }
-  auto d2h = [&](double* h, const double* d, size_t cnt) {
-    if (!rc && hipMemcpyAsync(h, d, cnt * sizeof(double), hipMemcpyDeviceToHost, c->stream) !=
-                   hipSuccess)
-      rc = fail("emergent copy failed");
-  };
-  if (intensity) d2h(intensity, d_int, A * K * n);
-  if (flux) d2h(flux, d_flux, A * n);
-  // the host vectors are read by the uploads until here
-  if (hipStreamSynchronize(c->stream) != hipSuccess && !rc) rc = fail("emergent kernel failed");
-  tm.read(c);
-  dfree(u_dt), dfree(d_iT), dfree(d_imu), dfree(d_ck), dfree(d_int), dfree(d_flux);
-  if (rc) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
-  return rc;
+  call.end();
+  call.download(intensity, d_int, A * K * n);
+  call.download(flux, d_flux, A * n);
+  return call.finish();   // the host vectors are read by the uploads until here
 }
 
 int frei_post_timing(frei_ctx* c, double* ms) {

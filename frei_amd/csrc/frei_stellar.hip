@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "../../include/frei_hip.h"
-#include "frei_device.h"
+#include "frei_host.h"
 
 using namespace frei;
 
@@ -49,12 +49,6 @@ constexpr int kTile = 4;   // spectra per block
 // at 3.0 points per bin the lane-per-bin form takes 0.232 ms against 0.256 ms, at 5.0 points
 // 0.302 ms against 0.201 ms: the crossover lies between, at about 4.
 constexpr double kWavePerBinFrom = 4.0;
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t _e = (expr);                                                             \
-    if (_e != hipSuccess) return set_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
 
 __device__ __forceinline__ double quiet_nan() {
   return __longlong_as_double(0x7ff8000000000000ll);
@@ -217,12 +211,14 @@ int frei_sspec_create(frei_sspec** out, int device, const double* flux, int n_sp
       hipMalloc((void**)&s->d_flux, nflux * sizeof(double)) != hipSuccess ||
       hipMalloc((void**)&s->d_wl, (size_t)n_hi * sizeof(double)) != hipSuccess) {
     frei_sspec_destroy(s);
+    (void)hipGetLastError();
     return set_error("frei_sspec_create: device allocation failed");
   }
   if (hipMemcpy(s->d_flux, flux, nflux * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(s->d_wl, wl_hi, (size_t)n_hi * sizeof(double), hipMemcpyHostToDevice) !=
           hipSuccess) {
     frei_sspec_destroy(s);
+    (void)hipGetLastError();
     return set_error("frei_sspec_create: host-to-device copy failed");
   }
   *out = s;
@@ -270,52 +266,31 @@ int frei_sspec_bin(frei_sspec* s, const double* wl_bins, int64_t n_bins, int for
   HIP_TRY(hipSetDevice(s->device));
   hipStream_t st = s->stream;
   const size_t total = (size_t)s->n_spec * n_bins;
-  if (int rc = grow(&s->d_pos, &s->pos_cap, pos.size())) return rc;
-  if (int rc = grow(&s->d_out, &s->out_cap, total)) return rc;
-  // (pos outlives the copy: the stream is synchronised before it is timed or returned from)
-  HIP_TRY(hipMemcpyAsync(s->d_pos, pos.data(), pos.size() * sizeof(int64_t),
-                         hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  auto cleanup = [&]() {
-    (void)hipStreamSynchronize(st);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e), e = nullptr;
-  };
-  if (kernel_ms) {
-    for (auto& e : ev)
-      if (hipEventCreate(&e) != hipSuccess) return cleanup(), set_error("hipEventCreate failed");
-    if (hipEventRecord(ev[0], st) != hipSuccess)
-      return cleanup(), set_error("stellar binning: timing event failed");
-  }
-  const unsigned tiles = (unsigned)((s->n_spec + kTile - 1) / kTile);
-  if (f == 1) {
-    dim3 grid((unsigned)((n_bins + 255) / 256), tiles);
-    sspec_lane_kernel<<<grid, 256, 0, st>>>(s->d_flux, s->d_wl, s->d_pos, n_bins, s->nhi,
-                                            s->n_spec, s->d_out);
-  } else {
-    switch (wave_group(mean_points)) {
-      case 4: launch_wave<4>(s, n_bins, tiles, st); break;
-      case 8: launch_wave<8>(s, n_bins, tiles, st); break;
-      case 16: launch_wave<16>(s, n_bins, tiles, st); break;
-      case 32: launch_wave<32>(s, n_bins, tiles, st); break;
-      default: launch_wave<64>(s, n_bins, tiles, st); break;
+  // d_pos and d_out are the handle's, kept between calls: the call owns nothing
+  DeviceCall call(st, "stellar binning");
+  call.check(grow(&s->d_pos, &s->pos_cap, pos.size()));
+  if (call.ok()) call.check(grow(&s->d_out, &s->out_cap, total));
+  call.copy_in(s->d_pos, pos.data(), pos.size());
+  call.begin(kernel_ms);
+  if (call.ok()) {
+    const unsigned tiles = (unsigned)((s->n_spec + kTile - 1) / kTile);
+    if (f == 1) {
+      dim3 grid((unsigned)((n_bins + 255) / 256), tiles);
+      sspec_lane_kernel<<<grid, 256, 0, st>>>(s->d_flux, s->d_wl, s->d_pos, n_bins, s->nhi,
+                                              s->n_spec, s->d_out);
+    } else {
+      switch (wave_group(mean_points)) {
+        case 4: launch_wave<4>(s, n_bins, tiles, st); break;
+        case 8: launch_wave<8>(s, n_bins, tiles, st); break;
+        case 16: launch_wave<16>(s, n_bins, tiles, st); break;
+        case 32: launch_wave<32>(s, n_bins, tiles, st); break;
+        default: launch_wave<64>(s, n_bins, tiles, st); break;
+      }
     }
   }
-  if (hipGetLastError() != hipSuccess)
-    return cleanup(), set_error("stellar binning kernel launch failed");
-  if (kernel_ms) {
-    float ms = 0;
-    if (hipEventRecord(ev[1], st) != hipSuccess || hipEventSynchronize(ev[1]) != hipSuccess ||
-        hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess)
-      return cleanup(), set_error("stellar binning: timing event failed");
-    *kernel_ms = ms;
-  }
-  if (hipStreamSynchronize(st) != hipSuccess)
-    return cleanup(), set_error("stellar binning kernel failed");
-  cleanup();
-  if (out) HIP_TRY(hipMemcpy(out, s->d_out, total * sizeof(double), hipMemcpyDeviceToHost));
-  return 0;
+  call.end();
+  call.download(out, s->d_out, total);
+  return call.finish();
 }
 
 }  // extern "C"

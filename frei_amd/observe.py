@@ -20,6 +20,8 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from ._device import (DeviceObject, broadened_source, i32ptr, library_rows, per_atmosphere,
+                      resident_or_host, select_rows, unknown_kind)
 from .engine import trapz_weights
 from .transit import default_radius
 from .twostream import BB
@@ -74,12 +76,15 @@ def star_library(planets, lam):
     return N.f64(np.array(rows)), np.array(select, dtype=np.int32)
 
 
-class Instrument:
+class Instrument(DeviceObject):
     """K channels on the native axis ``lam`` ([n_lam], µm): ``first`` and ``count`` [K] and the
     channels' ``weights`` back to back ([sum(count)], finite, >= 0, each channel's sum > 0),
     resident on ``device``.  Channels may overlap and come in any order."""
 
+    _destroy = "frei_obs_destroy"
+
     def __init__(self, lam, first, count, weights, device=0):
+        super().__init__(device)
         self.lam = N.f64(value(lam, "um"))
         self.first = np.ascontiguousarray(first, dtype=np.int64)
         self.count = np.ascontiguousarray(count, dtype=np.int64)
@@ -91,11 +96,6 @@ class Instrument:
         if self.weights.ndim != 1 or self.weights.size != int(np.maximum(self.count, 0).sum()):
             raise ValueError("weights must hold one value per covered point: "
                              f"{int(np.maximum(self.count, 0).sum())}, not {self.weights.size}")
-        self.device = device
-        self.form_used = None
-        self._handle = None
-        self._ms = 0.0
-        self._calls = 0
 
     @property
     def n_channels(self):
@@ -184,44 +184,12 @@ class Instrument:
         return cls._build(lam, spans, weights_of, "holds no point of the axis", device, False)
 
     # ------------------------------------------------------------------ device
-    def handle(self):
+    def _create(self, h):
         """frei_obs* of the instrument (plan and weights uploaded once)."""
-        if self._handle is None:
-            h = ctypes.c_void_p()
-            N.check(N.lib().frei_obs_create(
-                ctypes.byref(h), self.device, self.lam.size, self.first.size,
-                self.first.ctypes.data_as(_i64p), self.count.ctypes.data_as(_i64p),
-                N.dptr(self.weights)))
-            self._handle = h
-        return self._handle
-
-    def release(self):
-        if self._handle is not None:
-            N.lib().frei_obs_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
-
-    def timing(self, reset=False):
-        """(milliseconds, calls) of the kernels since the last reset (HIP events around the
-        kernels only: uploads and read-back excluded)."""
-        ms, n = self._ms, self._calls
-        if reset:
-            self._ms, self._calls = 0.0, 0
-        return ms, n
-
-    def _library(self, a, name):
-        if a is None:
-            return None
-        a = np.ascontiguousarray(np.atleast_2d(N.f64(a)))
-        if a.ndim != 2 or a.shape[1] != self.n_lam:
-            raise ValueError(f"{name} must be [n_lam] or [n_lib][n_lam] with n_lam = "
-                             f"{self.n_lam}, not {a.shape}")
-        return a
+        return N.lib().frei_obs_create(
+            ctypes.byref(h), self.device, self.lam.size, self.first.size,
+            self.first.ctypes.data_as(_i64p), self.count.ctypes.data_as(_i64p),
+            N.dptr(self.weights))
 
     def apply(self, x, num=None, den=None, select=None, scale=None, data=None, sigma=None,
               form=0, engine=None):
@@ -235,40 +203,17 @@ class Instrument:
         ``Broadening.apply(keep=True)`` left on the device.  ``form``
         0 picks the kernel from the points per channel, 1 forces one lane per channel, 2 one
         group of lanes per channel (``form_used`` records the choice)."""
-        ctx, brd = None, None
-        if hasattr(x, "owner") and hasattr(x, "serial"):
-            # a BroadenedSpectra (K13): the spectra lie on the device with its Broadening
-            brd, n_atm, single, x = x.handle(), x.n_atm, x.single, None
-        elif x is None:
-            if engine is None:
-                raise ValueError("pass x, or engine= for its resident spectra")
-            if engine.n_lam != engine.lam_um.size:
-                raise ValueError("a wavelength-slice engine cannot feed an instrument: a "
-                                 "channel may straddle slices")
-            ctx = engine._ctx
-            n_atm, single = getattr(engine, "n_atm", 1), not hasattr(engine, "n_atm")
-        else:
-            x = N.f64(getattr(x, "value", x))     # a Quantity's numbers as they are
-            if x.ndim not in (1, 2) or x.shape[-1] != self.n_lam:
-                raise ValueError(f"x must be [n_lam] or [n_atm][n_lam] with n_lam = "
-                                 f"{self.n_lam}, not {x.shape}")
-            single = x.ndim == 1
-            x = np.ascontiguousarray(np.atleast_2d(x))
-            n_atm = x.shape[0]
-        num, den = self._library(num, "num"), self._library(den, "den")
+        x, ctx, brd, n_atm, single, _ = resident_or_host(
+            x, engine, self.n_lam, ("an instrument", "a channel"))
+        num = library_rows(num, "num", self.n_lam)
+        den = library_rows(den, "den", self.n_lam)
         n_lib = 0
         if num is not None or den is not None:
             n_lib = (num if num is not None else den).shape[0]
             if num is not None and den is not None and num.shape != den.shape:
                 raise ValueError("num and den must hold the same number of rows")
-        sel = None
-        if select is not None:
-            sel = np.ascontiguousarray(select, dtype=np.int32)
-            if sel.shape != (n_atm,):
-                raise ValueError(f"select must have {n_atm} entries")
-        sc = None
-        if scale is not None:
-            sc = N.f64(np.broadcast_to(np.asarray(scale, dtype=float), (n_atm,)))
+        sel = select_rows(select, n_atm)
+        sc = per_atmosphere(scale, n_atm)
         if (data is None) != (sigma is None):
             raise ValueError("chi2 needs both data and sigma")
         K = self.n_channels
@@ -280,17 +225,14 @@ class Instrument:
             chi2 = np.empty(n_atm)
         obs = np.empty((n_atm, K))
         used, ms = ctypes.c_int(0), ctypes.c_double(0.0)
-        tail = (N.dptr(num), N.dptr(den), n_lib,
-                None if sel is None else sel.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                N.dptr(sc), N.dptr(data), N.dptr(sigma), int(form), N.dptr(obs), N.dptr(chi2),
-                ctypes.byref(used), ctypes.byref(ms))
+        tail = (N.dptr(num), N.dptr(den), n_lib, i32ptr(sel), N.dptr(sc), N.dptr(data),
+                N.dptr(sigma), int(form), N.dptr(obs), N.dptr(chi2), ctypes.byref(used),
+                ctypes.byref(ms))
         if brd is not None:
             N.check(N.lib().frei_obs_apply_brd(self.handle(), brd, n_atm, *tail))
         else:
             N.check(N.lib().frei_obs_apply(self.handle(), ctx, N.dptr(x), n_atm, *tail))
-        self.form_used = used.value
-        self._ms += ms.value
-        self._calls += 1
+        self._record(used, ms)
         if single:
             obs = obs[0]
             chi2 = None if chi2 is None else float(chi2[0])
@@ -332,19 +274,10 @@ def observe(instrument, kind, planets, lam, x=None, engine=None, weighting=None,
     resident spectra) for atmospheres whose stars are ``planets``'.  With ``broadening`` (a
     :class:`~frei_amd.broaden.Broadening`, K13) the spectrum is broadened first and stays on the
     device."""
-    if broadening is not None:
-        if kind not in ("flux", "eclipse", "transit"):
-            raise ValueError(f"unknown kind {kind!r}: 'flux', 'eclipse' or 'transit'")
-        if kind == "eclipse":
-            eclipse_scale(planets, R_p, R_star)     # its errors before any device work
-        x, engine = broadening.apply(x, engine=engine, keep=True), None
+    x, engine, star = broadened_source(kind, planets, lam, x, engine, R_p, R_star, broadening)
     kw = dict(data=data, sigma=sigma, engine=engine)
-    if kind == "flux":
-        return instrument.apply(x, **kw)
-    if kind == "eclipse":
-        scale = eclipse_scale(planets, R_p, R_star)     # before any device work
-        lib, select = star_library(planets, lam)
-        return instrument.apply(x, den=lib, select=select, scale=scale, **kw)
+    if kind in ("flux", "eclipse"):
+        return instrument.apply(x, **star, **kw)
     if kind == "transit":
         has_star = all(pl is not None for pl in planets)
         if weighting is None:
@@ -355,4 +288,4 @@ def observe(instrument, kind, planets, lam, x=None, engine=None, weighting=None,
             raise ValueError(f"unknown weighting {weighting!r}: 'stellar' or 'flat'")
         lib, select = star_library(planets, lam)
         return instrument.apply(x, num=lib, den=lib, select=select, **kw)
-    raise ValueError(f"unknown kind {kind!r}: 'flux', 'eclipse' or 'transit'")
+    raise unknown_kind(kind)

@@ -18,6 +18,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from ._device import DeviceObject
 from .units import unit_of, value, with_unit
 
 __all__ = ["StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum"]
@@ -25,11 +26,14 @@ __all__ = ["StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spec
 FLUX = "erg / (s cm3)"
 
 
-class StellarSpectra:
+class StellarSpectra(DeviceObject):
     """High-resolution spectra ``flux`` ([n_hi] or [n_spec][n_hi], erg s^-1 cm^-3) on
     ``wavelength`` ([n_hi], µm, strictly ascending), resident on ``device``."""
 
+    _destroy = "frei_sspec_destroy"
+
     def __init__(self, wavelength, flux, device=0):
+        super().__init__(device)
         self.wavelength = N.f64(value(wavelength, "um"))
         f = N.f64(value(flux, FLUX))
         if f.ndim not in (1, 2):
@@ -38,36 +42,16 @@ class StellarSpectra:
         self.flux = np.ascontiguousarray(np.atleast_2d(f))
         if self.wavelength.ndim != 1 or self.flux.shape[1] != self.wavelength.size:
             raise ValueError("flux must have one value per wavelength along its last axis")
-        self.device = device
-        self.form_used = None
-        self._handle = None
-        self._ms = 0.0
-        self._calls = 0
 
     @property
     def n_spec(self):
         return self.flux.shape[0]
 
-    def handle(self):
+    def _create(self, h):
         """frei_sspec* of the library (uploaded once)."""
-        if self._handle is None:
-            h = ctypes.c_void_p()
-            N.check(N.lib().frei_sspec_create(ctypes.byref(h), self.device, N.dptr(self.flux),
-                                              self.flux.shape[0], self.flux.shape[1],
-                                              N.dptr(self.wavelength)))
-            self._handle = h
-        return self._handle
-
-    def release(self):
-        if self._handle is not None:
-            N.lib().frei_sspec_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.release()
-        except Exception:
-            pass
+        return N.lib().frei_sspec_create(ctypes.byref(h), self.device, N.dptr(self.flux),
+                                         self.flux.shape[0], self.flux.shape[1],
+                                         N.dptr(self.wavelength))
 
     def bin(self, wl_bins, form=0, counts=False, out=True):
         """Every spectrum binned onto ``wl_bins`` (n_bins + 1 edges, µm), aligned with the
@@ -87,20 +71,10 @@ class StellarSpectra:
             self.handle(), N.dptr(wl_bins), nb, int(form), N.dptr(res),
             cnt.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), ctypes.byref(used),
             ctypes.byref(ms)))
-        self.form_used = used.value
-        self._ms += ms.value
-        self._calls += 1
+        self._record(used, ms)
         if res is not None and self.single:
             res = res[0]
         return (res, cnt) if counts else res
-
-    def timing(self, reset=False):
-        """(milliseconds, calls) of the binning kernels since the last reset (HIP events around
-        the kernel only: plan upload and read-back excluded)."""
-        ms, n = self._ms, self._calls
-        if reset:
-            self._ms, self._calls = 0.0, 0
-        return ms, n
 
 
 def binned_stellar_spectrum(wavelength, flux, wl_bins, lam, device=0):

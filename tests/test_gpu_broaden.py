@@ -182,6 +182,36 @@ def test_calls_and_rows_are_bitwise_reproducible(fa, form):
     assert np.all(np.abs(a1 - other) <= c["bound"]), q
 
 
+def test_errors_leave_the_handle_usable(fa):
+    """A refused call — by the library's argument checks or by its check of a resident source —
+    leaves handle and device as they were: the next apply gives the first one's bits."""
+    c = _case(257, 2, HALF[17])
+    p = np.logspace(np.log10(200.0), -6, 5)
+    b = fa.Broadening(c["lam"], c["kern"])
+    try:
+        good = b.apply(c["x"])
+        with pytest.raises(RuntimeError, match="form"):
+            b.apply(c["x"], form=max(fa.broaden.FORMS) + 1)
+        assert np.array_equal(b.apply(c["x"]), good)
+        lam = np.linspace(1.0, 2.0, 300)
+        tabs = {"1H2-16O": fa.OpacityTable(np.ones((5, 2, 300)), p, [1000.0, 2000.0])}
+        wide = fa.Engine(lam, p, tabs)
+        try:
+            with pytest.raises(RuntimeError, match="n_lam = 300 is not the broadener's 257"):
+                b.apply(None, engine=wide)
+        finally:
+            wide.close()
+        assert np.array_equal(b.apply(c["x"]), good)
+        kept = b.apply(c["x"], keep=True)
+        with pytest.raises(RuntimeError, match="form"):
+            b.apply(c["x"], form=-1)
+        with pytest.raises(RuntimeError, match="stale"):
+            kept.handle()
+        assert np.array_equal(b.apply(c["x"]), good)
+    finally:
+        b.release()
+
+
 def test_constant_spectrum_comes_back_exactly_in_form_1(fa):
     """With x = 1 the numerator's fma(w, 1, acc) is norm's acc + w, term by term; a power of two
     scales every partial sum exactly.  (Any other constant rounds w x and norm differently and is

@@ -208,6 +208,32 @@ def test_one_dimensional_library_gives_one_dimensional_result(fa, edge_case):
     assert calls == 1 and ms > 0.0
 
 
+def test_a_refused_call_leaves_the_library_usable(fa):
+    """2 spectra x 400 points onto 20 bins, then onto 7: a call the library refuses in between
+    leaves the handle, its kept plan and result buffers and the device as they were."""
+    rng = np.random.default_rng(20)
+    wl = np.sort(rng.uniform(1.0, 2.0, 400))
+    flux = 10 ** rng.uniform(3, 4, (2, 400))
+    bins, fewer = np.linspace(1.0, 2.0, 21), np.linspace(1.1, 1.9, 8)
+    lib = fa.StellarSpectra(wl, flux)
+    try:
+        good = lib.bin(bins)
+        assert good.shape == (2, 20) and np.all(np.isfinite(good))
+        with pytest.raises(RuntimeError, match="form"):
+            lib.bin(bins, form=3)
+        assert np.array_equal(lib.bin(bins), good)
+        with pytest.raises(RuntimeError, match="ascending"):
+            lib.bin(bins[::-1].copy())
+        small = lib.bin(fewer)                  # the kept buffers, reused for a smaller plan
+        with pytest.raises(RuntimeError, match="form"):
+            lib.bin(fewer, form=-1)
+        assert np.array_equal(lib.bin(fewer), small)
+        assert np.array_equal(lib.bin(bins), good)
+        assert lib.timing()[1] == 5
+    finally:
+        lib.release()
+
+
 @pytest.mark.parametrize("form", [1, 2])
 def test_nan_flux_poisons_exactly_its_bin(fa, edge_case, form):
     e = edge_case
