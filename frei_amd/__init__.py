@@ -14,6 +14,7 @@ from .core import (B_star, F_TOA, Grid, Planet, Spectrum, contribution_function,
 from .crosscorr import CrossCorrelation, CrossCorrelator, kp_vsys_map
 from .broaden import BroadenedSpectra, Broadening, BroadeningKernel
 from .emergent import gauss_angles
+from .stack import OrbitStack
 from .engine import Engine, balanced_edges, partition, trapz_weights
 from .observe import Instrument
 from .opacity import (OpacityTable, SeparableTable, binned_opacity, kappa,
@@ -34,4 +35,4 @@ __all__ = ["Planet", "Grid", "Spectrum", "effective_temperature", "wavelength_gr
            "batched_emission_spectra", "ChemistryTable", "BatchRecord", "BatchResult",
            "StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum",
            "level_radii", "Instrument", "gauss_angles", "CrossCorrelator", "CrossCorrelation",
-           "kp_vsys_map"]
+           "kp_vsys_map", "OrbitStack"]

@@ -1,4 +1,5 @@
-"""What the device-side objects share (StellarSpectra, Instrument, CrossCorrelator, Broadening):
+"""What the device-side objects share (StellarSpectra, Instrument, CrossCorrelator, Broadening,
+OrbitStack):
 the handle's lifecycle and the kernel timing (:class:`DeviceObject`), the choice between spectra
 resident on the device and a host array (:func:`resident_or_host`), and the argument checks of
 the calls that take a library, a ``select`` and numbers per atmosphere.  A new post-processing

@@ -138,6 +138,14 @@ SIGNATURES = {
     "frei_obs_apply_brd": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, ctypes.c_int,
                                           ctypes.POINTER(ctypes.c_int32), _dp, _dp, _dp,
                                           ctypes.c_int, _dp, _dp, _ip, _dp]),
+    "frei_ccf_keep": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "frei_stack_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_int, _dp, ctypes.c_int, _dp, _dp,
+                                         ctypes.c_int, _dp]),
+    "frei_stack_apply": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, _dp, ctypes.c_int,
+                                        ctypes.c_double, _dp, _dp, ctypes.c_double, _dp, _dp,
+                                        ctypes.c_int, _ip, _dp]),
+    "frei_stack_destroy": (ctypes.c_int, [_vp]),
 }
 
 _lib = None

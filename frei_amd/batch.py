@@ -402,7 +402,7 @@ class BatchResult(list):
                        data=data, sigma=sigma, R_p=R_p, R_star=R_star, broadening=broadening)
 
     def cross_correlate(self, cc, kind="eclipse", depth=None, R_p=None, R_star=None,
-                        offset=None, broadening=None):
+                        offset=None, broadening=None, keep=False, **kw):
         """Every atmosphere against high-resolution data over a grid of trial velocities
         (``cc``: :class:`~frei_amd.crosscorr.CrossCorrelator`, K12) ->
         :class:`~frei_amd.crosscorr.CrossCorrelation`.  ``kind``: "flux" takes the emergent
@@ -412,7 +412,10 @@ class BatchResult(list):
         radii).  Stars and radii as in :meth:`observe`; ``offset`` (a number per atmosphere) is
         subtracted from each template.  ``broadening``
         (:class:`~frei_amd.broaden.Broadening`, K13) broadens the spectra (for "transit" minus
-        the depth) on the device first: resident to resident, then the pre-pass."""
+        the depth) on the device first: resident to resident, then the pre-pass.  ``keep=True``
+        (and any further keyword, ``want=`` or ``form=``) goes to
+        :meth:`~frei_amd.crosscorr.CrossCorrelator.correlate`: the sums stay on the device for
+        :meth:`~frei_amd.stack.OrbitStack.stack` (K14)."""
         from .crosscorr import cross_correlate
         A = len(self)
         planets = self.planets if self.planets is not None else [None] * A
@@ -421,7 +424,8 @@ class BatchResult(list):
             x = self.transmission(R_p=R_p, R_star=R_star) if depth is None else depth
         return cross_correlate(cc, kind, planets, self.engine.lam_um, x=x,
                                engine=None if kind == "transit" else self.engine, R_p=R_p,
-                               R_star=R_star, offset=offset, broadening=broadening)
+                               R_star=R_star, offset=offset, broadening=broadening, keep=keep,
+                               **kw)
 
     def close(self):
         self.engine.close()

@@ -245,18 +245,21 @@ class Grid:
                        data=data, sigma=sigma, R_p=R_p, R_star=R_star, broadening=broadening)
 
     def cross_correlate(self, cc, spectrum, kind="eclipse", R_p=None, R_star=None, offset=None,
-                        broadening=None):
+                        broadening=None, keep=False, **kw):
         """``spectrum`` (the :class:`Spectrum` of emission_spectrum or transmission_spectrum)
         against high-resolution data over a grid of trial velocities (``cc``:
         :class:`~frei_amd.crosscorr.CrossCorrelator`, K12) ->
         :class:`~frei_amd.crosscorr.CrossCorrelation`.  ``kind``: "flux" the spectrum as it is,
         "eclipse" F_p / F_star (R_p / R_star)^2, "transit" minus the transit depth.  Star and
         radii as in :meth:`observe`; ``broadening`` broadens the spectrum (for "transit" minus
-        the depth) on the device first."""
+        the depth) on the device first.  ``keep=True`` (and any further keyword) goes to
+        :meth:`~frei_amd.crosscorr.CrossCorrelator.correlate`: the sums stay on the device for
+        :meth:`~frei_amd.stack.OrbitStack.stack` (K14)."""
         from .crosscorr import cross_correlate
         return cross_correlate(cc, kind, [self.planet], self.lam,
                                x=np.asarray(getattr(spectrum, "flux", spectrum), dtype=float),
-                               R_p=R_p, R_star=R_star, offset=offset, broadening=broadening)
+                               R_p=R_p, R_star=R_star, offset=offset, broadening=broadening,
+                               keep=keep, **kw)
 
     def emission_dashboard(self, *args, **kwargs):
         raise NotImplementedError("plotting is out of scope for the MI355X engine (SURVEY.md §2)")

@@ -25,8 +25,8 @@ from ._device import (DeviceObject, broadened_source, i32ptr, library_rows, per_
                       resident_or_host, select_rows, unknown_kind)
 from .units import value
 
-__all__ = ["CrossCorrelator", "CrossCorrelation", "kp_vsys_map", "FORMS", "PIXEL_CHUNK",
-           "C_KMS"]
+__all__ = ["CrossCorrelator", "CrossCorrelation", "KeptSums", "kp_vsys_map", "FORMS",
+           "PIXEL_CHUNK", "C_KMS"]
 
 C_KMS = 299792.458     # km/s
 # the kernel forms that exist (frei_ccf_apply's `form`; 0 picks among them)
@@ -51,6 +51,23 @@ def doppler_plan(lam, wl_data, velocities):
     return np.ascontiguousarray(j, dtype=np.int32), np.ascontiguousarray(t), n_clamped
 
 
+class KeptSums:
+    """What ``CrossCorrelator.correlate(keep=True)`` left on the device: the sums ``names`` of
+    ``n_atm`` atmospheres, for :meth:`frei_amd.stack.OrbitStack.stack`.  It goes stale at the
+    owner's next ``correlate`` or ``release``; using a stale one raises."""
+
+    def __init__(self, owner, serial, n_atm, single, names):
+        self.owner, self.serial, self.n_atm, self.single = owner, serial, n_atm, single
+        self.names = tuple(names)
+
+    def handle(self):
+        """frei_ccf* of the owner, after the staleness check."""
+        if self.owner._serial != self.serial or self.owner._handle is None:
+            raise RuntimeError("stale kept sums: their CrossCorrelator has correlated again or "
+                               "was released since")
+        return self.owner._handle
+
+
 class CrossCorrelation:
     """The sums of one :meth:`CrossCorrelator.correlate` call — ``sfg`` [n_atm][n_exp][n_vel],
     ``sg`` and ``sgg`` [n_atm][n_vel] (without the atmosphere axis for a 1-D ``x``; None where
@@ -64,12 +81,17 @@ class CrossCorrelation:
     are shallow against its continuum (with lines of a few per cent on a flat continuum about
     0.3 % of ``S_gg`` survives), and ``C_fg`` likewise.  ``offset=`` in ``correlate`` (for
     example each template's mean over the data's span) removes the continuum before the sums
-    are formed and is the remedy."""
+    are formed and is the remedy.
 
-    def __init__(self, sfg, sg, sgg, velocities, W, S_wf, S_wff, n_pix):
+    ``kept`` is the :class:`KeptSums` of a ``correlate(..., keep=True)`` (None otherwise): the
+    sums as they lie on the device, which :meth:`frei_amd.stack.OrbitStack.stack` turns into
+    K_p-V_sys maps without a copy to the host (K14)."""
+
+    def __init__(self, sfg, sg, sgg, velocities, W, S_wf, S_wff, n_pix, kept=None):
         self.sfg, self.sg, self.sgg = sfg, sg, sgg
         self.velocities = velocities
         self.W, self.S_wf, self.S_wff, self.n_pix = W, S_wf, S_wff, n_pix
+        self.kept = kept
 
     def _moments(self):
         if self.sfg is None or self.sg is None or self.sgg is None:
@@ -132,6 +154,8 @@ class CrossCorrelator(DeviceObject):
         self.W = float(np.sum(self.weights))
         self.S_wf = np.sum(self.a, axis=1)
         self.S_wff = np.sum(self.a * self.flux, axis=1)
+        self._serial = 0
+        self._keep_on = False
 
     @property
     def n_lam(self):
@@ -156,8 +180,13 @@ class CrossCorrelator(DeviceObject):
             ctypes.byref(h), self.device, self.n_lam, self.n_pix, self.n_vel, i32ptr(self.idx),
             N.dptr(self.frac), self.n_exp, N.dptr(self.a), N.dptr(self.weights))
 
+    def release(self):
+        self._serial += 1     # whatever was kept ends with the handle
+        self._keep_on = False
+        super().release()
+
     def correlate(self, x, den=None, select=None, scale=None, offset=None, form=0, engine=None,
-                  want=_SUMS):
+                  want=_SUMS, keep=False):
         """The sums of ``x`` ([n_lam] or [n_atm][n_lam]) against the data ->
         :class:`CrossCorrelation`.  The template is ``scale_m (x[m] / den[select_m]) -
         offset_m``: ``den`` an optional library ([n_lam] or [n_lib][n_lam]) with ``select``
@@ -168,7 +197,10 @@ class CrossCorrelator(DeviceObject):
         ``Broadening.apply(keep=True)`` left on the device.  ``form`` 0 picks the kernel, a
         member of ``FORMS`` forces it (``form_used`` records the choice).  ``want`` names the
         sums to compute (``"sfg"``, ``"sg"``, ``"sgg"``; the others are None and cost
-        nothing)."""
+        nothing).  ``keep=True`` also leaves the computed sums on the device (the result's
+        ``kept``, for :meth:`frei_amd.stack.OrbitStack.stack`, K14) until the next ``correlate``
+        or ``release``; ``want=()`` is then allowed: all three sums are computed and kept and
+        none is copied back."""
         want = (want,) if isinstance(want, str) else tuple(want)
         if any(k not in _SUMS for k in want):
             raise ValueError(f"want holds names other than {_SUMS}: {want}")
@@ -186,15 +218,21 @@ class CrossCorrelator(DeviceObject):
         tail = (N.dptr(den), n_lib, i32ptr(sel), N.dptr(sc), N.dptr(off), int(form),
                 N.dptr(out["sfg"]), N.dptr(out["sg"]), N.dptr(out["sgg"]), ctypes.byref(used),
                 ctypes.byref(ms))
+        handle = self.handle()
+        self._serial += 1                          # whatever was kept ends with this call
+        if bool(keep) != self._keep_on:            # switching keep mode off frees what was kept
+            N.check(N.lib().frei_ccf_keep(handle, 1 if keep else 0))
+            self._keep_on = bool(keep)
         if brd is not None:
-            N.check(N.lib().frei_ccf_apply_brd(self.handle(), brd, n_atm, *tail))
+            N.check(N.lib().frei_ccf_apply_brd(handle, brd, n_atm, *tail))
         else:
-            N.check(N.lib().frei_ccf_apply(self.handle(), ctx, N.dptr(x), n_atm, *tail))
+            N.check(N.lib().frei_ccf_apply(handle, ctx, N.dptr(x), n_atm, *tail))
         self._record(used, ms)
         if single:
             out = {k: None if v is None else v[0] for k, v in out.items()}
+        kept = KeptSums(self, self._serial, n_atm, single, want or _SUMS) if keep else None
         return CrossCorrelation(out["sfg"], out["sg"], out["sgg"], self.velocities, self.W,
-                                self.S_wf, self.S_wff, self.n_pix)
+                                self.S_wf, self.S_wff, self.n_pix, kept=kept)
 
 
 def kp_vsys_map(values, velocities, phases, Kp, Vsys, v_obs=0.0):

@@ -44,6 +44,10 @@ struct frei_ccf {
   double* d_a = nullptr;      // [n_exp][n_pix]  (form 1: coalesced along the pixels)
   double* d_at = nullptr;     // [p_pad][e_pad]  (form 2: an MFMA step's 16 exposures contiguous)
   double* d_w = nullptr;      // [p_pad]
+  // keep mode (frei_ccf_keep): the last successful apply's sums stay here for frei_stack_apply
+  bool keep = false;
+  double *k_sfg = nullptr, *k_sg = nullptr, *k_sgg = nullptr;
+  int k_atm = 0;
 };
 
 namespace {
@@ -384,7 +388,24 @@ std::string at2(const char* name, int64_t i, int64_t k) {
   return std::string(name) + "[" + std::to_string(i) + "][" + std::to_string(k) + "]";
 }
 
+// What keep mode left ends here (the stream is idle: every apply ends synchronised).
+void drop_kept(frei_ccf* c) {
+  if (c->k_sfg || c->k_sg || c->k_sgg) (void)hipSetDevice(c->device);
+  dfree(c->k_sfg);
+  dfree(c->k_sg);
+  dfree(c->k_sgg);
+  c->k_atm = 0;
+}
+
 }  // namespace
+
+namespace frei {
+int ccf_kept_sums(frei_ccf* c, CcfKept* out) {
+  if (!c) return set_error("null correlator");
+  *out = CcfKept{c->k_sfg, c->k_sg, c->k_sgg, c->k_atm, c->n_exp, c->n_vel, c->device};
+  return 0;
+}
+}  // namespace frei
 
 // ==================================================================== C ABI
 extern "C" {
@@ -477,6 +498,7 @@ int frei_ccf_destroy(frei_ccf* c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
+  drop_kept(c);
   for (void* p : {(void*)c->d_idx, (void*)c->d_frac, (void*)c->d_a, (void*)c->d_at,
                   (void*)c->d_w})
     if (p) (void)hipFree(p);
@@ -492,7 +514,11 @@ static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd*
                           const double* scale, const double* offset, int form, double* sfg,
                           double* sg, double* sgg, int* form_used, double* kernel_ms) {
   if (!c) return set_error("frei_ccf_apply: null handle");
-  if (!sfg && !sg && !sgg) return set_error("frei_ccf_apply: sfg, sg and sgg are all null");
+  if (!sfg && !sg && !sgg && !c->keep)
+    return set_error("frei_ccf_apply: sfg, sg and sgg are all null");
+  // the sums to compute: those asked for; in keep mode with none asked for, all three
+  const bool all = !sfg && !sg && !sgg;
+  const bool w_fg = sfg || all, w_g = sg || all, w_gg = sgg || all;
   if (!x && !ctx && !brd) return set_error("frei_ccf_apply: x and ctx are both null");
   if (n_atm < 1) return set_error("frei_ccf_apply: n_atm must be >= 1");
   if (form < 0 || form > 2)
@@ -507,6 +533,7 @@ static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd*
   if (form_used) *form_used = f;
 
   HIP_TRY(hipSetDevice(c->device));
+  drop_kept(c);   // what an earlier call kept ends here, whether or not this call succeeds
   hipStream_t st = rows.stream;
   const size_t A = (size_t)n_atm, n = (size_t)c->n_lam, V = (size_t)c->n_vel,
                E = (size_t)c->n_exp;
@@ -522,12 +549,12 @@ static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd*
   const double* d_scale = call.upload(scale, A);
   const double* d_off = call.upload(offset, A);
   double* d_y = result(prepass, A * n);
-  double* d_sfg = result(sfg, A * E * V);
-  double* d_sg = result(sg, A * V);
-  double* d_sgg = result(sgg, A * V);
-  double* p_sfg = result(nc > 1 && sfg, (size_t)nc * A * E * V);
-  double* p_sg = result(nc > 1 && sg, (size_t)nc * A * V);
-  double* p_sgg = result(nc > 1 && sgg, (size_t)nc * A * V);
+  double* d_sfg = result(w_fg, A * E * V);
+  double* d_sg = result(w_g, A * V);
+  double* d_sgg = result(w_gg, A * V);
+  double* p_sfg = result(nc > 1 && w_fg, (size_t)nc * A * E * V);
+  double* p_sg = result(nc > 1 && w_g, (size_t)nc * A * V);
+  double* p_sgg = result(nc > 1 && w_gg, (size_t)nc * A * V);
   call.begin(kernel_ms);
   if (call.ok()) {
     const double* src = u_x ? u_x : rows.rows;
@@ -559,18 +586,18 @@ static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd*
     const unsigned bz = (unsigned)((n_atm + kAT - 1) / kAT);
     if (f == 1) {
       a.e_tiles = (c->n_exp + kET - 1) / kET;
-      if (sfg)
+      if (w_fg)
         ccf_valu_kernel<false><<<dim3(bz, (unsigned)(nc * a.e_tiles), bx), 64 * kWaves, 0, st>>>(a);
-      if (sg || sgg)
+      if (w_g || w_gg)
         ccf_valu_kernel<true><<<dim3(bz, (unsigned)nc, bx), 64 * kWaves, 0, st>>>(a);
     } else {
       // exposure blocks of 16 spread evenly over the fewest tiles of at most 4
-      const int cb = sfg ? c->e_pad / 16 : 0, ty = (cb + 3) / 4;
+      const int cb = w_fg ? c->e_pad / 16 : 0, ty = (cb + 3) / 4;
       const int nb = ty ? (cb + ty - 1) / ty : 0;
       a.e_tiles = ty ? ty : 1;
       const dim3 grid((unsigned)((n_atm + 3) / 4), (unsigned)(nc * a.e_tiles),
                       (unsigned)((c->n_vel + 15) / 16));
-      if (sg || sgg) launch_mfma<true>(nb, grid, a, st);
+      if (w_g || w_gg) launch_mfma<true>(nb, grid, a, st);
       else launch_mfma<false>(nb, grid, a, st);
     }
     if (nc > 1) {
@@ -588,7 +615,19 @@ static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd*
   call.download(sfg, d_sfg, A * E * V);
   call.download(sg, d_sg, A * V);
   call.download(sgg, d_sgg, A * V);
-  return call.finish();
+  if (c->keep) {
+    call.keep(d_sfg);
+    call.keep(d_sg);
+    call.keep(d_sgg);
+  }
+  const int rc = call.finish();
+  if (!rc && c->keep) {   // complete: finish() synchronised the stream
+    c->k_sfg = d_sfg;
+    c->k_sg = d_sg;
+    c->k_sgg = d_sgg;
+    c->k_atm = n_atm;
+  }
+  return rc;
 }
 
 int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const double* den,
@@ -597,6 +636,13 @@ int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const
                    double* kernel_ms) {
   return ccf_apply_impl(c, ctx, x, nullptr, n_atm, den, n_lib, select, scale, offset, form, sfg,
                         sg, sgg, form_used, kernel_ms);
+}
+
+int frei_ccf_keep(frei_ccf* c, int on) {
+  if (!c) return set_error("frei_ccf_keep: null handle");
+  c->keep = on != 0;
+  if (!c->keep) drop_kept(c);
+  return 0;
 }
 
 int frei_ccf_apply_brd(frei_ccf* c, frei_brd* src, int n_atm, const double* den, int n_lib,

@@ -551,6 +551,17 @@ struct BrdRows {
 };
 int brd_kept_rows(frei_brd* b, BrdRows* out);
 }  // namespace frei
+struct frei_ccf;
+namespace frei {
+// K12 (frei_crosscorr.hip): what the correlator's last apply kept in keep mode — sfg
+// [n_atm][n_exp][n_vel], sg and sgg [n_atm][n_vel] on `device`, complete (its stream was
+// synchronised); a sum that was not computed is null, all three are null with nothing kept.
+struct CcfKept {
+  const double *sfg, *sg, *sgg;
+  int n_atm, n_exp, n_vel, device;
+};
+int ccf_kept_sums(frei_ccf* c, CcfKept* out);
+}  // namespace frei
 struct frei_xsec;
 namespace frei {
 // K6 (frei_binning.hip): bin one species into table rows d_tab + row_off[kp * n_T + kt].

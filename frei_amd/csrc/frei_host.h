@@ -63,6 +63,7 @@ int h2d(T* d, const T* h, size_t n, hipStream_t st) {
 //   if (call.ok()) { kernel<<<..., st>>>(...); }
 //   call.end();
 //   call.download(y, d_y, n);
+//   call.keep(d_y);                              // optional: d_y outlives a successful finish()
 //   return call.finish();
 // Host arrays passed to upload() and download() must live until finish() returns.
 class DeviceCall {
@@ -124,8 +125,11 @@ class DeviceCall {
       rc_ = set_error(what_ + ": timing event failed");
   }
 
-  // p (from alloc) outlives a successful finish() as the caller's; a failed one frees it.
-  void keep(void* p) { kept_ = p; }
+  // p (from alloc; null is ignored) outlives a successful finish() as the caller's; a failed
+  // one frees it.  Any number of buffers may be kept.
+  void keep(void* p) {
+    if (p) kept_.push_back(p);
+  }
 
   // Synchronises the stream, reads the timer, destroys the events, frees what the call owns
   // and returns the status.
@@ -138,7 +142,7 @@ class DeviceCall {
     for (hipEvent_t e : ev_)
       if (e) (void)hipEventDestroy(e);
     for (void* p : owned_)
-      if (rc_ || p != kept_) (void)hipFree(p);
+      if (rc_ || std::find(kept_.begin(), kept_.end(), p) == kept_.end()) (void)hipFree(p);
     if (rc_) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
     return rc_;
   }
@@ -151,7 +155,7 @@ class DeviceCall {
   double* ms_ = nullptr;
   hipEvent_t ev_[2] = {nullptr, nullptr};
   std::vector<void*> owned_;
-  void* kept_ = nullptr;
+  std::vector<void*> kept_;
 };
 
 // Where a consumer (an instrument, a correlator, a broadener) reads its spectra

@@ -600,7 +600,8 @@ int frei_ccf_create(frei_ccf** out, int device, int64_t n_lam, int64_t n_pix, in
  * form: 0 automatic (form 2 from 9 exposures, form 1 below: the measured crossover), 1 or 2 as
  * above; *form_used receives the form that ran.
  * Outputs sfg[n_atm][n_exp][n_vel], sg[n_atm][n_vel], sgg[n_atm][n_vel]: any may be NULL, not all
- * three; nothing is computed or allocated for an absent one.  *form_used and *kernel_ms (HIP
+ * three (but see keep mode, frei_ccf_keep below); nothing is computed or allocated for an absent
+ * one.  *form_used and *kernel_ms (HIP
  * events around the kernels only) may be NULL.  Errors (handle and context stay usable): null
  * handle, all outputs null, x and ctx both null, a select entry outside [0, n_lib), a context
  * of another shape or device.
@@ -705,6 +706,89 @@ int frei_obs_apply_brd(frei_obs* o, frei_brd* src, int n_atm, const double* num,
                        const double* den, int n_lib, const int32_t* select, const double* scale,
                        const double* data, const double* sigma, int form, double* obs,
                        double* chi2, int* form_used, double* kernel_ms);
+
+/*
+ * Keep mode of a correlator.  frei_ccf_keep(c, 1) switches it on: every later successful
+ * frei_ccf_apply / frei_ccf_apply_brd then also leaves the sums it computed in device buffers
+ * the handle owns, complete, until the next apply (successful or not once its arguments are
+ * accepted), frei_ccf_keep(c, 0) or frei_ccf_destroy; frei_stack_apply reads them there.  The
+ * sums computed are those whose host pointer is given; in keep mode all three host pointers may
+ * be NULL, and all three sums are then computed and kept and none is copied back.  What is copied
+ * back is bitwise what is kept.  frei_ccf_keep(c, 0) frees the buffers and restores the default:
+ * with keep off "sfg, sg and sgg are all null" stays an error and nothing else changes.
+ * Error: a null handle.
+ */
+int frei_ccf_keep(frei_ccf* c, int on);
+
+/*
+ * Orbital stack (K14): a detection statistic formed from the sums of frei_ccf_apply and summed
+ * over the exposures along trial orbits, one K_p-V_sys map per atmosphere.  The reference has no
+ * counterpart; this is the definition.
+ * A stacker holds the n_vel >= 2 trial velocities vel[n_vel] of the values (finite, strictly
+ * ascending; not assumed uniform), n_exp >= 1 exposures, n_kp >= 1 trial orbits with
+ * dv[n_kp][n_exp], the planet's line-of-sight velocity of trial k at exposure e (finite; formed
+ * by the caller, K_p[k] sin(2 pi phase_e) for a circular orbit, and never recomputed on the
+ * device), v_obs[n_exp] (finite) and n_vsys >= 1 systemic velocities vsys[n_vsys] (finite, any
+ * order).  frei_stack_create checks all of it on the host, naming the first offending index, and
+ * touches no device: the arrays are uploaded by the first frei_stack_apply and stay resident on
+ * `device` with the handle from then on.
+ *
+ * Statistic, per atmosphere m, exposure e and velocity v, by exactly these IEEE operations in
+ * this order, never contracted (frei_amd.crosscorr.CrossCorrelation._moments, .ccf, .loglike):
+ *   gbar = sg[m][v] / W
+ *   C_fg = sfg[m][e][v] - gbar * S_wf[e]
+ *   V_g  = sgg[m][v] - sg[m][v] * gbar
+ *   V_f  = S_wff[e] - (S_wf[e] * S_wf[e]) / W                        (formed on the host)
+ *   statistic 1 (ccf):     values = C_fg / sqrt(V_f * V_g)
+ *   statistic 2 (loglike): values = (-(n_eff / 2)) * log(((V_f - 2 * C_fg) + V_g) / W)
+ * Division and square root are the correctly rounded ones; log is the device library's.  With
+ * statistic 0 sfg already holds the values [n_atm][n_exp][n_vel]; sg, sgg, W, S_wf, S_wff and
+ * n_eff are ignored and may be NULL or 0.  Nothing is checked for sign: a non-positive variance
+ * gives the NaN or inf of the host methods.
+ *
+ * Stack, per atmosphere m, trial k and systemic velocity s, with f = values[m][e][:]:
+ *   u = (vsys[s] + dv[k][e]) + v_obs[e]                              (two additions, this order)
+ *   u clamped to [vel[0], vel[n_vel-1]]
+ *   j = the largest index with vel[j] <= u, limited to n_vel - 2     (a binary search)
+ *   t = (u - vel[j]) / (vel[j+1] - vel[j])
+ *   val = f[j] + t * (f[j+1] - f[j])                                 (three operations)
+ *   map[m][k][s] = sum of val over e = 0 .. n_exp - 1, ascending, one accumulator from 0, plain
+ *     additions.
+ * Beyond the ends of vel the end value holds (j = 0, t = 0 below; j = n_vel - 2, t = 1 above).
+ * A NaN or inf in values[m][e][i] reaches exactly the outputs (m, k, s) whose bracket at exposure
+ * e is j = i or j = i - 1, whatever t is (0 * NaN also touches).  One lane owns one (k, s) and a
+ * tile of 8 atmospheres: bracket and t are formed once for the tile.
+ * form 1 searches a copy of vel in LDS (n_vel <= FREI_STACK_LDS_VEL), form 2 searches vel in
+ * global memory (any n_vel); form 0 takes form 1 where it fits.  The forms give the same bits.
+ * No atomics; the order of summation depends on n_exp alone: results are bitwise the same from
+ * call to call and between the forms, row m of a batched call is bitwise the call on that row
+ * alone, an output (k, s) is bitwise unchanged when other trials or systemic velocities are added
+ * to or dropped from the handle, and the map of statistic 1 or 2 is bitwise the map of statistic
+ * 0 fed with the `values` the same call returned.
+ *
+ * Source of the sums: host arrays sfg[n_atm][n_exp][n_vel], sg and sgg [n_atm][n_vel] (uploaded
+ * for the call; statistic 0 needs sfg alone), or all three NULL with `kept`: a correlator in keep
+ * mode, whose last apply's sums are read where they lie (statistic 0 stacks its kept sfg).
+ * map[n_atm][n_kp][n_vsys] is required; values[n_atm][n_exp][n_vel] (what was stacked) may be
+ * NULL.  *form_used and *kernel_ms (HIP events around the statistic and stack kernels only) may
+ * be NULL.  Errors, all found before any device call (handles stay usable): a null handle or a
+ * null map; n_atm < 1; a statistic outside 0 .. 2 or a form outside 0 .. 2; form 1 with n_vel
+ * beyond FREI_STACK_LDS_VEL; neither host sums nor a kept source; host sums without sfg, or
+ * without sg or sgg for statistic 1 or 2; statistic 1 or 2 without S_wf, S_wff or with W = 0; a
+ * correlator that holds nothing kept, or lacks a kept sum the statistic needs; kept sums whose
+ * n_atm, n_exp or n_vel differ from the call's or the stacker's; different devices; n_kp or
+ * n_atm / 8 beyond the launch grid (65535).
+ */
+#define FREI_STACK_LDS_VEL 2048
+typedef struct frei_stack frei_stack;
+int frei_stack_create(frei_stack** out, int device, int n_exp, int n_vel, const double* vel,
+                      int n_kp, const double* dv, const double* v_obs, int n_vsys,
+                      const double* vsys);
+int frei_stack_apply(frei_stack* s, frei_ccf* kept, int n_atm, const double* sfg,
+                     const double* sg, const double* sgg, int statistic, double W,
+                     const double* S_wf, const double* S_wff, double n_eff, double* map,
+                     double* values, int form, int* form_used, double* kernel_ms);
+int frei_stack_destroy(frei_stack* s);
 
 #ifdef __cplusplus
 }
