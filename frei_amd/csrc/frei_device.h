@@ -416,7 +416,7 @@ __host__ __device__ inline int64_t part_at(int idx, int bx, int nbx, int ns4) {
 }
 
 // launchers (frei_kernels.hip)
-void launch_sweep(int dir, const SweepArgs& a, int nblocks, bool fast, hipStream_t st);
+void launch_sweep(int dir, const SweepArgs& a, int nblocks, hipStream_t st);
 void launch_sweep_fast(int dir, int S, int depth, int pf, bool nan_check, bool shared,
                        const FastArgs& a, int nblocks, hipStream_t st);
 // The atmosphere-tiled per-species sweep of a batched chemistry context: one block sweeps one

@@ -17,12 +17,54 @@
 // Numerics: fp64 throughout, compiled with -ffp-contract=off and the reference's
 // expression order, so results differ from NumPy only by the last-ulp differences of
 // exp/expm1/sqrt (ocml vs libm).  See DESIGN.md "Parity".
+#include <type_traits>
 #include <unordered_map>
 
 #include "frei_device.h"
 #include "frei_math.h"
 
 namespace frei {
+
+// ---------------------------------------------------------------- launch helpers
+// The one way a run-time value becomes a template argument: pick<a, b, c>(v, f) calls f with
+// std::integral_constant<., x> for the first listed x equal to v, the last when none is.  Each
+// launcher lists exactly the values its kernel is built for and nests picks only where every
+// combination is (no product of lists adds a kernel variant nothing launches).
+template <auto V, auto... Rest, typename F>
+static void pick(decltype(V) v, F&& f) {
+  if constexpr (sizeof...(Rest) == 0) {
+    f(std::integral_constant<decltype(V), V>{});
+  } else {
+    if (v == V) f(std::integral_constant<decltype(V), V>{});
+    else pick<Rest...>(v, f);
+  }
+}
+
+// The one launch with dynamic LDS: above 64 KiB a kernel must opt in first
+// (hipFuncAttributeMaxDynamicSharedMemorySize), raised whenever a launch needs more than the
+// kernel was given so far (deeper atmospheres: the partial-sum rows grow with the step count).
+static void lds_optin(const void* kernel, size_t lds) {
+  if (lds <= 65536) return;
+  static std::unordered_map<const void*, size_t> optin;   // the largest size set per kernel
+  size_t& have = optin[kernel];
+  if (lds > have) {
+    (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    have = lds;
+  }
+}
+template <typename K, typename... Args>
+static void launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st,
+                       const Args&... args) {
+  lds_optin(reinterpret_cast<const void*>(kernel), lds);
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+}
+// Dynamic LDS of a one-lane, tiled, two-wavelength or grouped-lane sweep launch (chained or
+// not): at least a.min_lds bytes (FREI_SWEEP_LDS_KB), which caps the blocks resident per CU at
+// 160 KiB / min_lds, so the dispatcher cannot stack three or four blocks on one CU while others
+// hold one (small slices: the launch ends with its most loaded CU).
+static size_t with_min_lds(const FastArgs& a, size_t lds) {
+  return lds > (size_t)a.min_lds ? lds : (size_t)a.min_lds;
+}
 
 // ---------------------------------------------------------------- diagnostic trace
 // FREI_TRACE builds only (tools/trace_probe.py): thread 0 of every block of the sweeps and
@@ -145,40 +187,23 @@ __device__ __forceinline__ void two_stream_g(double w0, double g0, double dtau, 
               pi_w * ((B1 * (chi + xi) - psi * B2) + q * ((xi + psi) - chi)));
 }
 
-// Species-summed opacity at one wavelength (opacity.py:250-269).  FAST: every term is
-// exactly two T-bracket rows of the layer's own pressure slab (pressure on a node).
-template <int S, bool FAST>
+// Species-summed opacity at one wavelength (opacity.py:250-269), any table layout (the tables
+// with every pressure on a node take the sweep_fast forms).
 __device__ __forceinline__ double kappa_at(const TermP* __restrict__ t, int nS, int64_t j,
                                            double sig) {
   double tot = 0.0;
-  if constexpr (FAST) {
-    double v[2 * S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) {  // issue every table load before the first use
-      v[2 * s] = __builtin_nontemporal_load(t[s].row[0] + j);
-      v[2 * s + 1] = __builtin_nontemporal_load(t[s].row[1] + j);
+  for (int s = 0; s < nS; ++s) {
+    double acc;
+    if (t[s].nrow < 0) {  // single-T table: scipy interp1d over pressure
+      const double lo = t[s].row[0][j], hi = t[s].row[1][j];
+      acc = ((hi - lo) / t[s].dx) * t[s].x1 + lo;
+    } else {
+      acc = 0.0;
+      for (int r = 0; r < t[s].nrow; ++r) acc = acc + t[s].row[r][j] * t[s].w[r];
     }
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-      const double acc = (0.0 + v[2 * s] * t[s].w[0]) + v[2 * s + 1] * t[s].w[1];
-      double ops = t[s].mmr * acc;
-      if (S > 1) ops = isnan(ops) ? 0.0 : ops;  // xarray nansum for S > 1 (Q8)
-      tot = (s == 0) ? ops : tot + ops;
-    }
-  } else {
-    for (int s = 0; s < nS; ++s) {
-      double acc;
-      if (t[s].nrow < 0) {  // single-T table: scipy interp1d over pressure
-        const double lo = t[s].row[0][j], hi = t[s].row[1][j];
-        acc = ((hi - lo) / t[s].dx) * t[s].x1 + lo;
-      } else {
-        acc = 0.0;
-        for (int r = 0; r < t[s].nrow; ++r) acc = acc + t[s].row[r][j] * t[s].w[r];
-      }
-      double ops = t[s].mmr * acc;
-      if (nS > 1) ops = isnan(ops) ? 0.0 : ops;
-      tot = (s == 0) ? ops : tot + ops;
-    }
+    double ops = t[s].mmr * acc;
+    if (nS > 1) ops = isnan(ops) ? 0.0 : ops;  // xarray nansum for S > 1 (Q8)
+    tot = (s == 0) ? ops : tot + ops;
   }
   return tot + sig;  // k includes sigma (Q1)
 }
@@ -284,7 +309,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // ---------------------------------------------------------------- K1: sweep
-template <int DIR, int S, bool FAST>
+template <int DIR>
 __global__ __launch_bounds__(kBlock) void sweep_kernel(SweepArgs a) {
   if (!a.force && *a.conv) return;
   extern __shared__ double red[];  // [wave][step][4]
@@ -316,7 +341,7 @@ __global__ __launch_bounds__(kBlock) void sweep_kernel(SweepArgs a) {
   for (int k = 0; k < ns; ++k) {
     const StepP sp = a.steps[k];
     const int i = sp.layer;
-    const double kap = kappa_at<S, FAST>(a.terms + (int64_t)k * nS, nS, j, sig);
+    const double kap = kappa_at(a.terms + (int64_t)k * nS, nS, j, sig);
     const double dtau = sp.dm * kap;             // twostream.py:227-231
     const double w0 = fm::div(sig, sig + kap);   // twostream.py:376-378
     double B1, B2, F1u, F2d;
@@ -1168,35 +1193,15 @@ __global__ __launch_bounds__(kBlock) void sweep_tile_kernel(FastArgs a) {
   }
 }
 
-static size_t sweep_shm(const void* kernel, const FastArgs& a, size_t shm);
-template <int DIR, int S, int AT>
-static void launch_tile_t(const FastArgs& a, int nblocks, hipStream_t st) {
-  const auto kernel = sweep_tile_kernel<DIR, S, AT>;
-  hipLaunchKernelGGL(kernel, dim3(nblocks, (a.n_atm + AT - 1) / AT), dim3(kBlock),
-                     sweep_shm(reinterpret_cast<const void*>(kernel), a,
-                               tile_lds_bytes(AT, a.n_steps)),
-                     st, a);
-}
-template <int DIR, int AT>
-static void launch_tile_s(int S, const FastArgs& a, int nblocks, hipStream_t st) {
-  switch (S) {
-    case 2: return launch_tile_t<DIR, 2, AT>(a, nblocks, st);
-    case 3: return launch_tile_t<DIR, 3, AT>(a, nblocks, st);
-    case 4: return launch_tile_t<DIR, 4, AT>(a, nblocks, st);
-    case 5: return launch_tile_t<DIR, 5, AT>(a, nblocks, st);
-    case 6: return launch_tile_t<DIR, 6, AT>(a, nblocks, st);
-    case 7: return launch_tile_t<DIR, 7, AT>(a, nblocks, st);
-    default: return launch_tile_t<DIR, 8, AT>(a, nblocks, st);
-  }
-}
 void launch_sweep_tile(int dir, int S, int AT, const FastArgs& a, int nblocks, hipStream_t st) {
-  if (dir == kEmit) {
-    if (AT == 4) launch_tile_s<kEmit, 4>(S, a, nblocks, st);
-    else launch_tile_s<kEmit, 2>(S, a, nblocks, st);
-  } else {
-    if (AT == 4) launch_tile_s<kAbsorb, 4>(S, a, nblocks, st);
-    else launch_tile_s<kAbsorb, 2>(S, a, nblocks, st);
-  }
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    pick<4, 2>(AT, [&](auto at) {
+      pick<2, 3, 4, 5, 6, 7, 8>(S, [&](auto s) {
+        launch_lds(sweep_tile_kernel<D(), s(), at()>, dim3(nblocks, (a.n_atm + at() - 1) / at()),
+                   dim3(kBlock), with_min_lds(a, tile_lds_bytes(at(), a.n_steps)), st, a);
+      });
+    });
+  });
 }
 
 // ---------------------------------------------------------------- K1, grouped-lane form
@@ -1723,66 +1728,34 @@ __global__ __launch_bounds__(kBlock, 1) void sweep_pair_kernel(
   TRACE_PUT(2);
 }
 
-static size_t sweep_shm(const void* kernel, const FastArgs& a, size_t shm);
 // Two wavelengths per lane (sweep_pair_kernel): nblocks = ceil(n_lam / 512).
 void launch_sweep_pair(int dir, const FastArgs& a, int nblocks, hipStream_t st) {
   const size_t shm = (size_t)red_lds_doubles(2, a.n_steps) * sizeof(double);
-  const dim3 grid(nblocks, a.n_atm > 1 ? a.n_atm : 1);
-  if (dir == kEmit) {
-    const auto k = sweep_pair_kernel<kEmit>;
-    hipLaunchKernelGGL(k, grid, dim3(kBlock), sweep_shm(reinterpret_cast<const void*>(k), a, shm),
-                       st, a, a.steps, a.F_up, a.F_down, a.part, a.dtaus);
-  } else {
-    const auto k = sweep_pair_kernel<kAbsorb>;
-    hipLaunchKernelGGL(k, grid, dim3(kBlock), sweep_shm(reinterpret_cast<const void*>(k), a, shm),
-                       st, a, a.steps, a.F_up, a.F_down, a.part, a.dtaus);
-  }
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    launch_lds(sweep_pair_kernel<D()>, dim3(nblocks, a.n_atm > 1 ? a.n_atm : 1), dim3(kBlock),
+               with_min_lds(a, shm), st, a, a.steps, a.F_up, a.F_down, a.part, a.dtaus);
+  });
 }
 
-// Dynamic LDS of a one-lane / grouped-lane sweep launch: at least a.min_lds bytes
-// (FREI_SWEEP_LDS_KB), which caps the blocks resident per CU at 160 KiB / min_lds, so the
-// dispatcher cannot stack three or four blocks on one CU while others hold one (small slices:
-// the launch ends with its most loaded CU).  Above 64 KiB the kernel opts in first.
-static size_t sweep_shm(const void* kernel, const FastArgs& a, size_t shm) {
-  const size_t s = shm > (size_t)a.min_lds ? shm : (size_t)a.min_lds;
-  if (s > 65536) {
-    static std::unordered_map<const void*, size_t> optin;
-    size_t& have = optin[kernel];
-    if (s > have) {
-      (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s);
-      have = s;
-    }
-  }
-  return s;
+// LDS of a sweep block with the step table and the record scratch beside the partial sums
+// (grouped-lane: nw waves; one-lane with LDS step records: kBlock / 64)
+static size_t lds_steps_bytes(const FastArgs& a, int nw = kBlock / 64) {
+  return (size_t)red_lds_doubles(a.red_rows, a.n_steps, nw) * sizeof(double) +
+         (size_t)a.n_steps * sizeof(FastStepS) + (size_t)rec_scratch_doubles(a) * sizeof(double);
 }
 
 // Q lanes per wavelength, NW waves: 64 NW / Q wavelengths per block.
 void launch_sweep_group(int dir, int Q, int NW, const FastArgs& a, int nblocks,
                         hipStream_t st) {
-  const size_t shm = (size_t)red_lds_doubles(a.red_rows, a.n_steps, NW) * sizeof(double) +
-                     (size_t)a.n_steps * sizeof(FastStepS) +
-                     (size_t)rec_scratch_doubles(a) * sizeof(double);
-  const dim3 grid(nblocks, a.n_atm > 1 ? a.n_atm : 1);
-  auto go = [&](auto kernel, int nw) {
-    const size_t s = sweep_shm(reinterpret_cast<const void*>(kernel), a, shm);
-    hipLaunchKernelGGL(kernel, grid, dim3(64 * nw), s, st, a, a.ssteps, a.F_up, a.F_down,
-                       a.part, a.dtaus);
-  };
-  if (NW == 8) {
-    if (Q == 4) {
-      if (dir == kEmit) go(sweep_group_kernel<kEmit, 4, 8>, 8);
-      else go(sweep_group_kernel<kAbsorb, 4, 8>, 8);
-    } else {
-      if (dir == kEmit) go(sweep_group_kernel<kEmit, 2, 8>, 8);
-      else go(sweep_group_kernel<kAbsorb, 2, 8>, 8);
-    }
-  } else if (Q == 4) {
-    if (dir == kEmit) go(sweep_group_kernel<kEmit, 4, 4>, 4);
-    else go(sweep_group_kernel<kAbsorb, 4, 4>, 4);
-  } else {
-    if (dir == kEmit) go(sweep_group_kernel<kEmit, 2, 4>, 4);
-    else go(sweep_group_kernel<kAbsorb, 2, 4>, 4);
-  }
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    pick<4, 2>(Q, [&](auto q) {
+      pick<8, 4>(NW, [&](auto nw) {
+        launch_lds(sweep_group_kernel<D(), q(), nw()>, dim3(nblocks, a.n_atm > 1 ? a.n_atm : 1),
+                   dim3(64 * nw()), with_min_lds(a, lds_steps_bytes(a, nw())), st, a, a.ssteps,
+                   a.F_up, a.F_down, a.part, a.dtaus);
+      });
+    });
+  });
 }
 
 
@@ -2131,42 +2104,21 @@ void sweep_pipe_kernel(FastArgs a, const FastStepS* __restrict__ ss, double* __r
   sweep_pipe_body<DIR, NC, M, PF, false>(a, ss, Fu, Fd, part, dtaus, lds, blockIdx.x, gridDim.x);
 }
 
-template <int DIR, int NC, int M, int PF>
-static void launch_pipe_t(const FastArgs& a, int nblocks, hipStream_t st) {
-  const size_t shm = (size_t)pipe_lds_doubles(NC, M, a.n_steps) * sizeof(double);
-  // (the record scratch reuses the LDS ring, which holds far more than 2 n_layers + n_tnodes)
-  // dynamic LDS above 64 KiB needs the kernel's opt-in, raised whenever a launch needs more
-  // (deeper atmospheres: the partial-sum rows grow with the step count)
-  static size_t attr = 0;
-  if (shm > attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sweep_pipe_kernel<DIR, NC, M, PF>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-    attr = shm;
-  }
-  hipLaunchKernelGGL((sweep_pipe_kernel<DIR, NC, M, PF>),
-                     dim3(nblocks, a.n_atm > 1 ? a.n_atm : 1), dim3(256 * NC), shm, st, a,
-                     a.ssteps, a.F_up, a.F_down, a.part, a.dtaus);
-}
-
-template <int NC, int PF>
-static void launch_pipe_nc(int dir, const FastArgs& a, int nblocks, hipStream_t st) {
-  if (dir == kEmit) launch_pipe_t<kEmit, NC, 2, PF>(a, nblocks, st);
-  else launch_pipe_t<kAbsorb, NC, 2, PF>(a, nblocks, st);
-}
-
 // NC consumers (64 NC wavelengths) per block, M = 2 steps per producer and phase (M = 4 needs
 // more than the 128 VGPRs of 4 waves per SIMD and spills), table rows PF phases ahead.
+// (the record scratch reuses the LDS ring, which holds far more than 2 n_layers + n_tnodes)
 void launch_sweep_pipe(int dir, int NC, int PF, const FastArgs& a, int nblocks,
                        hipStream_t st) {
-  if (PF == 2) {
-    if (NC == 4) launch_pipe_nc<4, 2>(dir, a, nblocks, st);
-    else if (NC == 2) launch_pipe_nc<2, 2>(dir, a, nblocks, st);
-    else launch_pipe_nc<1, 2>(dir, a, nblocks, st);
-  } else {
-    if (NC == 4) launch_pipe_nc<4, 1>(dir, a, nblocks, st);
-    else if (NC == 2) launch_pipe_nc<2, 1>(dir, a, nblocks, st);
-    else launch_pipe_nc<1, 1>(dir, a, nblocks, st);
-  }
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    pick<4, 2, 1>(NC, [&](auto nc) {
+      pick<2, 1>(PF, [&](auto pf) {
+        launch_lds(sweep_pipe_kernel<D(), nc(), 2, pf()>,
+                   dim3(nblocks, a.n_atm > 1 ? a.n_atm : 1), dim3(256 * nc()),
+                   pipe_lds_bytes(nc(), 2, a.n_steps), st, a, a.ssteps, a.F_up, a.F_down, a.part,
+                   a.dtaus);
+      });
+    });
+  });
 }
 
 size_t pipe_lds_bytes(int NC, int M, int ns) {
@@ -2949,27 +2901,14 @@ void sweep_pipe_chain_kernel(FastArgs a, UpdateArgs u, const FastStepS* __restri
 void launch_sweep_pipe_chain(int dir, int PF, const FastArgs& a, const UpdateArgs& u,
                              int nblocks, hipStream_t st) {
   const int nL = u.su.n_layers;
-  size_t shm = pipe_lds_bytes(4, 2, a.n_steps);
-  const size_t ushm = (size_t)(2 * nL + u.su.n_tnodes) * sizeof(double);
-  if (ushm > shm) shm = ushm;
-  auto go = [&](auto kernel) {
-    static std::unordered_map<const void*, size_t> optin;
-    size_t& have = optin[reinterpret_cast<const void*>(kernel)];
-    if (shm > have) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      have = shm;
-    }
-    hipLaunchKernelGGL(kernel, dim3(nL + nblocks), dim3(1024), shm, st, a, u,
-                       a.ssteps, a.F_up, a.F_down, a.part, a.dtaus);
-  };
-  if (PF == 2) {
-    if (dir == kEmit) go(sweep_pipe_chain_kernel<kEmit, 2>);
-    else go(sweep_pipe_chain_kernel<kAbsorb, 2>);
-  } else {
-    if (dir == kEmit) go(sweep_pipe_chain_kernel<kEmit, 1>);
-    else go(sweep_pipe_chain_kernel<kAbsorb, 1>);
-  }
+  const size_t shm = std::max(pipe_lds_bytes(4, 2, a.n_steps),
+                              (size_t)(2 * nL + u.su.n_tnodes) * sizeof(double));
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    pick<2, 1>(PF, [&](auto pf) {
+      launch_lds(sweep_pipe_chain_kernel<D(), pf()>, dim3(nL + nblocks), dim3(1024), shm, st, a,
+                 u, a.ssteps, a.F_up, a.F_down, a.part, a.dtaus);
+    });
+  });
 }
 
 // ---------------------------------------------------------------- trailing update (round 6)
@@ -3277,24 +3216,12 @@ void launch_sweep_pipe_tail(int dir, int PF, const FastArgs& a, const UpdateArgs
                             int nbx, int n_tail, double* clear, hipStream_t st) {
   const size_t shm = pipe_tail_lds_bytes(a.n_steps, u.su.n_tnodes);
   const int64_t n_clear = (int64_t)nbx * a.n_steps * 4;
-  auto go = [&](auto kernel) {
-    static std::unordered_map<const void*, size_t> optin;
-    size_t& have = optin[reinterpret_cast<const void*>(kernel)];
-    if (shm > have) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      have = shm;
-    }
-    hipLaunchKernelGGL(kernel, dim3(nbx + n_tail), dim3(1024), shm, st, a, u, a.ssteps, a.F_up,
-                       a.F_down, a.dtaus, clear, n_clear);
-  };
-  if (PF == 2) {
-    if (dir == kEmit) go(sweep_pipe_tail_kernel<kEmit, 2>);
-    else go(sweep_pipe_tail_kernel<kAbsorb, 2>);
-  } else {
-    if (dir == kEmit) go(sweep_pipe_tail_kernel<kEmit, 1>);
-    else go(sweep_pipe_tail_kernel<kAbsorb, 1>);
-  }
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    pick<2, 1>(PF, [&](auto pf) {
+      launch_lds(sweep_pipe_tail_kernel<D(), pf()>, dim3(nbx + n_tail), dim3(1024), shm, st, a, u,
+                 a.ssteps, a.F_up, a.F_down, a.dtaus, clear, n_clear);
+    });
+  });
 }
 
 // Fill n 8-byte slots with kPoisonT ("not published"): the trailing update's partial buffers
@@ -3326,35 +3253,29 @@ __global__ __launch_bounds__(kBlock, 1) void sweep_fast_chain_kernel(
                                                           red, blockIdx.x - nL, gridDim.x - nL);
 }
 
-template <int PD, int PF>
-static void launch_fast_chain_t(int dir, const FastArgs& a, const UpdateArgs& u, int nblocks,
-                                size_t shm, hipStream_t st) {
-  const int nL = u.su.n_layers;
-  const auto kernel = dir == kEmit ? sweep_fast_chain_kernel<kEmit, PD, PF>
-                                   : sweep_fast_chain_kernel<kAbsorb, PD, PF>;
-  hipLaunchKernelGGL(kernel, dim3(nL + nblocks), dim3(kBlock),
-                     sweep_shm(reinterpret_cast<const void*>(kernel), a, shm), st, a, u,
-                     a.ssteps, a.F_up, a.F_down, a.part, a.dtaus);
-}
+// Steps in flight (PD) and load distance in steps (PF) of the contracted one-lane sweep from the
+// run-time depth and pf: two or four steps in flight, loads 16 or 8 steps ahead, else PD's own
+// distance (returned as 0: the pickers below list {16, 8, 0} for either PD).
+static int fast_pd(int depth) { return depth >= 4 ? 4 : 2; }
+static int fast_pf_or_0(int pf) { return pf >= 16 ? 16 : pf >= 8 ? 8 : 0; }
 
-// The one-lane sweep chained to the previous sweep's fused update u: depth 2 or 4 steps in
-// flight, loads pf (8, 16; 0: the depth) steps ahead, as launch_sweep_fast chooses them.
+// The one-lane sweep chained to the previous sweep's fused update u (u's workgroups first, then
+// the sweep blocks): depth 2 or 4 steps in flight, loads pf (8, 16; 0: the depth) steps ahead,
+// as launch_sweep_fast chooses them.
 void launch_sweep_fast_chain(int dir, int depth, int pf, const FastArgs& a, const UpdateArgs& u,
                              int nblocks, hipStream_t st) {
-  size_t shm = (size_t)red_lds_doubles(a.red_rows, a.n_steps) * sizeof(double) +
-               (size_t)a.n_steps * sizeof(FastStepS) +
-               (size_t)rec_scratch_doubles(a) * sizeof(double);
-  const size_t ushm = (size_t)(2 * u.su.n_layers + u.su.n_tnodes) * sizeof(double);
-  if (ushm > shm) shm = ushm;
-  if (depth >= 4) {
-    if (pf >= 16) launch_fast_chain_t<4, 16>(dir, a, u, nblocks, shm, st);
-    else if (pf >= 8) launch_fast_chain_t<4, 8>(dir, a, u, nblocks, shm, st);
-    else launch_fast_chain_t<4, 4>(dir, a, u, nblocks, shm, st);
-  } else {
-    if (pf >= 16) launch_fast_chain_t<2, 16>(dir, a, u, nblocks, shm, st);
-    else if (pf >= 8) launch_fast_chain_t<2, 8>(dir, a, u, nblocks, shm, st);
-    else launch_fast_chain_t<2, 2>(dir, a, u, nblocks, shm, st);
-  }
+  const int nL = u.su.n_layers;
+  const size_t shm =
+      std::max(lds_steps_bytes(a), (size_t)(2 * nL + u.su.n_tnodes) * sizeof(double));
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    pick<4, 2>(fast_pd(depth), [&](auto pd) {
+      pick<16, 8, 0>(fast_pf_or_0(pf), [&](auto f) {
+        launch_lds(sweep_fast_chain_kernel<D(), pd(), f() ? f() : pd()>, dim3(nL + nblocks),
+                   dim3(kBlock), with_min_lds(a, shm), st, a, u, a.ssteps, a.F_up, a.F_down,
+                   a.part, a.dtaus);
+      });
+    });
+  });
 }
 
 // The chained launch of a grouped-lane sweep: the update workgroups of u ahead of nblocks sweep
@@ -3362,32 +3283,18 @@ void launch_sweep_fast_chain(int dir, int depth, int pf, const FastArgs& a, cons
 void launch_sweep_chain(int dir, int Q, int NW, const FastArgs& a, const UpdateArgs& u,
                         int nblocks, hipStream_t st) {
   const int nL = u.su.n_layers;
-  const int nU = (nL + NW / 4 - 1) / (NW / 4);
-  size_t shm = (size_t)red_lds_doubles(a.red_rows, a.n_steps, NW) * sizeof(double) +
-               (size_t)a.n_steps * sizeof(FastStepS) +
-               (size_t)rec_scratch_doubles(a) * sizeof(double);
-  const size_t ushm = (size_t)(NW / 4) * (2 * nL + u.su.n_tnodes) * sizeof(double);
-  if (ushm > shm) shm = ushm;
-  auto go = [&](auto kernel) {
-    const size_t s = sweep_shm(reinterpret_cast<const void*>(kernel), a, shm);
-    hipLaunchKernelGGL(kernel, dim3(nU + nblocks), dim3(64 * NW), s, st, a, u, a.ssteps,
-                       a.F_up, a.F_down, a.part, a.dtaus);
-  };
-  if (NW == 8) {
-    if (Q == 4) {
-      if (dir == kEmit) go(sweep_chain_kernel<kEmit, 4, 8>);
-      else go(sweep_chain_kernel<kAbsorb, 4, 8>);
-    } else {
-      if (dir == kEmit) go(sweep_chain_kernel<kEmit, 2, 8>);
-      else go(sweep_chain_kernel<kAbsorb, 2, 8>);
-    }
-  } else if (Q == 4) {
-    if (dir == kEmit) go(sweep_chain_kernel<kEmit, 4, 4>);
-    else go(sweep_chain_kernel<kAbsorb, 4, 4>);
-  } else {
-    if (dir == kEmit) go(sweep_chain_kernel<kEmit, 2, 4>);
-    else go(sweep_chain_kernel<kAbsorb, 2, 4>);
-  }
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    pick<4, 2>(Q, [&](auto q) {
+      pick<8, 4>(NW, [&](auto nw) {
+        constexpr int kHalves = nw() / 4;   // update layers per workgroup (sweep_chain_kernel)
+        const size_t shm = std::max(lds_steps_bytes(a, nw()),
+                                    (size_t)kHalves * (2 * nL + u.su.n_tnodes) * sizeof(double));
+        launch_lds(sweep_chain_kernel<D(), q(), nw()>,
+                   dim3((nL + kHalves - 1) / kHalves + nblocks), dim3(64 * nw()),
+                   with_min_lds(a, shm), st, a, u, a.ssteps, a.F_up, a.F_down, a.part, a.dtaus);
+      });
+    });
+  });
 }
 
 // ---------------------------------------------------------------- standalone kernels
@@ -3412,7 +3319,7 @@ __global__ void kappa_kernel(int64_t n, const TermP* terms, int nS, const double
                              double* k) {
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  k[j] = kappa_at<1, false>(terms, nS, j, sig[j]);
+  k[j] = kappa_at(terms, nS, j, sig[j]);
 }
 
 __global__ void gen_table_kernel(double* tab, const double* base, const double* fp,
@@ -3930,105 +3837,63 @@ __global__ void fill_kernel(double* x, int64_t n, double v) {
 }
 
 // ---------------------------------------------------------------- launchers
-template <int DIR, int S, bool FAST>
-static void launch_sweep_t(const SweepArgs& a, int nblocks, hipStream_t st) {
+void launch_sweep(int dir, const SweepArgs& a, int nblocks, hipStream_t st) {
   const size_t shm = (size_t)(kBlock / 64) * a.n_steps * 4 * sizeof(double);
-  hipLaunchKernelGGL((sweep_kernel<DIR, S, FAST>), dim3(nblocks), dim3(kBlock), shm, st, a);
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    launch_lds(sweep_kernel<D()>, dim3(nblocks), dim3(kBlock), shm, st, a);
+  });
 }
 
-template <int DIR>
-static void launch_sweep_dir(const SweepArgs& a, int nblocks, bool, hipStream_t st) {
-  launch_sweep_t<DIR, 1, false>(a, nblocks, st);
-}
-
-void launch_sweep(int dir, const SweepArgs& a, int nblocks, bool fast, hipStream_t st) {
-  if (dir == kEmit) launch_sweep_dir<kEmit>(a, nblocks, fast, st);
-  else launch_sweep_dir<kAbsorb>(a, nblocks, fast, st);
-}
-
-template <int DIR, int S, int PD, bool NC, bool SH, bool MM1 = false, int PF = PD>
-static void launch_fast_t(const FastArgs& a, int nblocks, hipStream_t st) {
-  const size_t shm = (size_t)red_lds_doubles(a.red_rows, a.n_steps) * sizeof(double) +
-                     (SH ? (size_t)a.n_steps * sizeof(FastStepS) +
-                               (size_t)rec_scratch_doubles(a) * sizeof(double)
-                         : 0);
-  const auto kernel = sweep_fast_kernel<DIR, S, PD, NC, SH, MM1, PF>;
-  hipLaunchKernelGGL(kernel, dim3(nblocks, a.n_atm > 1 ? a.n_atm : 1), dim3(kBlock),
-                     sweep_shm(reinterpret_cast<const void*>(kernel), a, shm), st, a, a.steps,
-                     a.ssteps, a.F_up, a.F_down, a.part, a.dtaus);
-}
-
-// the contracted one-table sweep (S = 1, unit mmr) with prefetch distance pf (0: = PD)
-template <int DIR, int PD, bool SH>
-static void launch_fast_pf(int pf, const FastArgs& a, int nblocks, hipStream_t st) {
-  if (pf >= 16) return launch_fast_t<DIR, 1, PD, false, SH, true, 16>(a, nblocks, st);
-  if (pf >= 8) return launch_fast_t<DIR, 1, PD, false, SH, true, 8>(a, nblocks, st);
-  return launch_fast_t<DIR, 1, PD, false, SH, true, PD>(a, nblocks, st);
-}
-
-template <int DIR, int PD, bool NC, bool SH>
-static void launch_fast_dir(int S, const FastArgs& a, int nblocks, hipStream_t st) {
-  switch (S) {
-    case 1:
-      if (a.unit_mmr && !NC) return launch_fast_t<DIR, 1, PD, false, SH, true>(a, nblocks, st);
-      return launch_fast_t<DIR, 1, PD, NC, SH>(a, nblocks, st);
-    case 2: return launch_fast_t<DIR, 2, PD, NC, SH>(a, nblocks, st);
-    case 3: return launch_fast_t<DIR, 3, PD, NC, SH>(a, nblocks, st);
-    case 4: return launch_fast_t<DIR, 4, PD, NC, SH>(a, nblocks, st);
-    case 5: return launch_fast_t<DIR, 5, PD, NC, SH>(a, nblocks, st);
-    case 6: return launch_fast_t<DIR, 6, PD, NC, SH>(a, nblocks, st);
-    case 7: return launch_fast_t<DIR, 7, PD, NC, SH>(a, nblocks, st);
-    default: return launch_fast_t<DIR, 8, PD, NC, SH>(a, nblocks, st);
-  }
-}
-
-template <int PD, bool NC, bool SH>
-static void launch_fast_pd(int dir, int S, const FastArgs& a, int nblocks, hipStream_t st) {
-  if (dir == kEmit) launch_fast_dir<kEmit, PD, NC, SH>(S, a, nblocks, st);
-  else launch_fast_dir<kAbsorb, PD, NC, SH>(S, a, nblocks, st);
-}
-
-template <bool SH>
-static void launch_fast_sh(int dir, int S, int depth, int pf, bool nan_check, const FastArgs& a,
-                           int nblocks, hipStream_t st) {
-  if (pf > depth && S == 1 && a.unit_mmr && !nan_check && depth >= 2) {
-    // the contracted table with loads issued pf steps ahead
-    if (depth >= 4) {
-      if (dir == kEmit) launch_fast_pf<kEmit, 4, SH>(pf, a, nblocks, st);
-      else launch_fast_pf<kAbsorb, 4, SH>(pf, a, nblocks, st);
-    } else {
-      if (dir == kEmit) launch_fast_pf<kEmit, 2, SH>(pf, a, nblocks, st);
-      else launch_fast_pf<kAbsorb, 2, SH>(pf, a, nblocks, st);
-    }
-    return;
-  }
-  if (depth == 1 && pf == 2 && S == 1 && a.unit_mmr && !nan_check) {
-    // one step per coefficient block, loads two steps ahead (fewer registers: 5 waves per SIMD)
-    if (dir == kEmit) launch_fast_t<kEmit, 1, 1, false, SH, true, 2>(a, nblocks, st);
-    else launch_fast_t<kAbsorb, 1, 1, false, SH, true, 2>(a, nblocks, st);
-    return;
-  }
-  if (depth >= 4 && S == 1 && !nan_check) {  // 4 steps in flight: small slices, one table
-    if (a.unit_mmr) {
-      if (dir == kEmit) launch_fast_t<kEmit, 1, 4, false, SH, true>(a, nblocks, st);
-      else launch_fast_t<kAbsorb, 1, 4, false, SH, true>(a, nblocks, st);
-    } else {
-      if (dir == kEmit) launch_fast_t<kEmit, 1, 4, false, SH>(a, nblocks, st);
-      else launch_fast_t<kAbsorb, 1, 4, false, SH>(a, nblocks, st);
-    }
-  } else if (depth >= 2) {
-    if (nan_check) launch_fast_pd<2, true, SH>(dir, S, a, nblocks, st);
-    else launch_fast_pd<2, false, SH>(dir, S, a, nblocks, st);
-  } else {
-    if (nan_check) launch_fast_pd<1, true, SH>(dir, S, a, nblocks, st);
-    else launch_fast_pd<1, false, SH>(dir, S, a, nblocks, st);
-  }
-}
-
+// The one-lane sweep <DIR, S, PD, NANCHK, SH, MM1, PF>.  Which (S, PD, NANCHK, MM1, PF) exist:
+//   MM1 (S = 1, unit mmr: the contracted table, never with the NaN test):
+//     PD 4 or 2 with PF 16, 8 or PD;  PD 1 with PF 2 or 1
+//   otherwise PF = PD:  S = 1 without the NaN test: PD 4, 2, 1;  any other (S, NANCHK): PD 2, 1
 void launch_sweep_fast(int dir, int S, int depth, int pf, bool nan_check, bool shared,
                        const FastArgs& a, int nblocks, hipStream_t st) {
-  if (shared) launch_fast_sh<true>(dir, S, depth, pf, nan_check, a, nblocks, st);
-  else launch_fast_sh<false>(dir, S, depth, pf, nan_check, a, nblocks, st);
+  const bool one = S == 1 && !nan_check;   // one table, no NaN test
+  const bool mm1 = one && a.unit_mmr;
+  int PD = depth >= 2 ? 2 : 1, PF = 0;     // (PF 0: PD's own distance)
+  if (mm1 && pf > depth && depth >= 2) {
+    // the contracted table with loads issued pf steps ahead
+    PD = fast_pd(depth);
+    PF = fast_pf_or_0(pf);
+  } else if (mm1 && depth == 1 && pf == 2) {
+    // one step per coefficient block, loads two steps ahead (fewer registers: 5 waves per SIMD)
+    PF = 2;
+  } else if (one && depth >= 4) {  // 4 steps in flight: small slices, one table
+    PD = 4;
+  }
+  pick<kEmit, kAbsorb>(dir, [&](auto D) {
+    pick<true, false>(shared, [&](auto SH) {
+      auto go = [&](auto s, auto pd, auto nanchk, auto m1, auto f) {
+        const size_t shm = SH() ? lds_steps_bytes(a)
+                                : (size_t)red_lds_doubles(a.red_rows, a.n_steps) * sizeof(double);
+        launch_lds(sweep_fast_kernel<D(), s(), pd(), nanchk(), SH(), m1(), f() ? f() : pd()>,
+                   dim3(nblocks, a.n_atm > 1 ? a.n_atm : 1), dim3(kBlock), with_min_lds(a, shm),
+                   st, a, a.steps, a.ssteps, a.F_up, a.F_down, a.part, a.dtaus);
+      };
+      constexpr std::integral_constant<int, 1> k1{};
+      constexpr std::integral_constant<int, 4> k4{};
+      constexpr std::integral_constant<int, 0> k0{};
+      if (mm1 && PD == 1) {
+        pick<2, 0>(PF, [&](auto f) { go(k1, k1, std::false_type{}, std::true_type{}, f); });
+      } else if (mm1) {
+        pick<4, 2>(PD, [&](auto pd) {
+          pick<16, 8, 0>(PF, [&](auto f) { go(k1, pd, std::false_type{}, std::true_type{}, f); });
+        });
+      } else if (PD == 4) {
+        go(k1, k4, std::false_type{}, std::false_type{}, k0);
+      } else {
+        pick<2, 1>(PD, [&](auto pd) {
+          pick<true, false>(nan_check, [&](auto nanchk) {
+            pick<1, 2, 3, 4, 5, 6, 7, 8>(S, [&](auto s) {
+              go(s, pd, nanchk, std::false_type{}, k0);
+            });
+          });
+        });
+      }
+    });
+  });
 }
 
 __global__ void nan_scan_kernel(const double* __restrict__ x, int64_t n, int* flag) {

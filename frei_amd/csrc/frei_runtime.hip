@@ -336,14 +336,33 @@ int sweep_pf(const frei_ctx* c, bool eff, int S_run, int depth) {
 // The two-wavelength sweep's requirements besides the contracted NaN-free table, one lane per
 // wavelength, global step records and no chained launch: an even slice, enough one-lane blocks
 // (or FREI_LAM2=1), a depth-2 coefficient block loading at most two steps ahead, and the staged
-// partial sums.  run_sweep (fast_form), frei_ctx_path and the batched step-table choice
-// (build_meta) all decide by it.
+// partial sums.  The sweep's plan (sweep_plan) and the batched step-table choice (build_meta,
+// which runs before the contracted table the plan needs exists) decide by it.
 bool lam2_static(const frei_ctx* c, int depth, int pf) {
   return c->lam2 != 0 && c->nlam % 2 == 0 && (c->lam2 > 0 || lam2_blocks(c)) && depth == 2 &&
          pf <= 2 && c->red_stage && staged_sums_fit(c->nL - 1);
 }
 
-bool lam2_form(const frei_ctx* c);   // (below: fast_form)
+// What one sweep launches, decided in one place (sweep_plan, below): run_sweep launches from it,
+// frei_ctx_path reports it, build_contracted asks it whether the lazy contraction applies and
+// the graph-replay key hashes it (all int: no padding bytes).
+enum SweepForm : int { kGeneric = 0, kOneLane, kTiled, kLam2, kGrouped, kPipe };
+struct SweepPlan {
+  int form;        // SweepForm
+  int chain;       // chained launches apply to this context's sweeps
+  int merge;       // chained: this launch's leading workgroups run the pending update
+  int defer_own;   // chained: this sweep's own update waits for the next launch
+  int tail_nT;     // update workgroups trailing the producer/consumer sweep (0: none)
+  int S_run, depth, pf, Q, NW, NC, pipe_pf, red_rows;
+  int nan_check;   // the per-species sweep tests for NaN (never on the contracted table)
+  int lds_steps;   // shared-bracket step records (one bracket for all species)
+  int tile;        // atmospheres per block of the tiled form
+  int rec_on;      // the sweep forms its own step records
+  int fused;       // reduce + update in one launch
+  int nb_run;      // partial-sum columns the sweep writes
+  int whole_table; // lazy K3: every row must be contracted before this sweep
+};
+SweepPlan sweep_plan(const frei_ctx* c, bool pending, bool defer);
 
 // Atmospheres per block of a chemistry batch's sweep (0: not a chemistry batch).  The tiled
 // kernel is instantiated for S = 2..8 and reduces with the staged sums of the one-lane sweep it
@@ -456,7 +475,7 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   for (int s = 0; s < S; ++s) tabs[s] = c->sp[s].d_tab;
   // lazy K3: the sweeps that read this table take two wavelengths per lane (the form run_sweep
   // launches for a loop's sweeps), one atmosphere
-  c->lazy_on = c->lazy_k3 && !batch && lam2_form(c);
+  c->lazy_on = c->lazy_k3 && !batch && sweep_plan(c, false, false).form == kLam2;
   c->eff_complete = !c->lazy_on;
   if (c->lazy_on) {
     dfree(c->d_kvalid);
@@ -656,8 +675,9 @@ int build_meta(frei_ctx* c) {
   return 0;
 }
 
-AtmStride atm_stride(frei_ctx* c);
+AtmStride atm_stride(const frei_ctx* c);
 
+// The steps of sweep_plan, which calls each once.
 // Lanes per wavelength of the sweep: the grouped-lane kernel (2 or 4 lanes) when the slice
 // leaves about one wave per SIMD or less (contracted table, LDS step table), else 1.
 int group_lanes(const frei_ctx* c) {
@@ -684,20 +704,19 @@ int pipe_consumers(const frei_ctx* c) {
   return nc;
 }
 
-SetupArgs setup_args(frei_ctx* c);
-
 // Sweeps form their own step records in their prologue (and the update kernels skip writing
 // them) when the sweep reads the shared-bracket records from LDS — every form on the contracted
 // table with shared brackets — and the mixing ratios are fixed (no T-dependent chemistry).
-bool records_in_sweep(frei_ctx* c) {
+// NC: pipe_consumers.
+bool records_in_sweep(const frei_ctx* c, int NC) {
   if (!(c->rec_sweep && c->fast && c->eff && c->shared && !c->chem_on)) return false;
   // auto: not for batched contexts (every (block, atmosphere) would form the records: C5 -2 %,
   // profiles/r02_ab_rec_sweep.txt), nor for the producer/consumer sweep unless its launches
   // are chained (neutral to slower on their own; a chained sweep must form its records)
-  return c->rec_sweep > 0 || (c->n_atm == 1 && (pipe_consumers(c) == 0 || c->chain == 2));
+  return c->rec_sweep > 0 || (c->n_atm == 1 && (NC == 0 || c->chain == 2));
 }
 
-SetupArgs setup_args(frei_ctx* c) {
+SetupArgs setup_args(const frei_ctx* c) {
   SetupArgs u{};
   u.n_layers = c->nL;
   u.n_species = c->eff ? 1 : c->S;
@@ -790,54 +809,110 @@ void drop_pending(frei_ctx* c) {
 
 // reduce + update fused into one launch: one atmosphere, exchange local or P2P (RCCL and the
 // host hook need the rank's sums in memory between the two kernels)
-bool fused_ok(frei_ctx* c) {
+bool fused_ok(const frei_ctx* c) {
   return c->fused_update && c->n_atm == 1 && !c->comm && !(c->nranks > 1 && c->host_ag) &&
          (2 * (size_t)c->nL + c->tnodes.size()) * sizeof(double) <= 32 * 1024;
 }
 
-// This sweep can run chained: a grouped-lane or one-lane (two or more steps in flight) sweep
-// of the contracted table forming its own step records, fused update, stream launches (no graph
-// capture).
-// Not while per-sweep HIP events are on (frei_timing): events around a chained launch would also
-// cover the deferred update it runs, including its wait for the peers' sums, so a timed run
-// launches sweep and update separately and the events time the sweep alone.  Not when ranks
-// share this device (frei_comm_shared_device): a chained launch's sweep blocks
-// spin on the update workgroups, which wait for every rank's sums, and could hold the CUs
+// Sweep and update share launches (chained launches, the trailing update) only as stream
+// launches (no graph capture) and not while per-sweep HIP events are on (frei_timing): events
+// around such a launch would also cover the update it runs, including its wait for the peers'
+// sums, so a timed run launches sweep and update separately and the events time the sweep
+// alone.  Nor when ranks share this device (frei_comm_shared_device): the launch's sweep or
+// update blocks spin on workgroups that wait for every rank's sums, and could hold the CUs
 // another rank's kernels need.
-bool chain_ready(frei_ctx* c) {
-  if (!(c->chain && c->fast && c->eff && c->shared && records_in_sweep(c) && fused_ok(c) &&
-        !c->use_graph && !c->keys && !c->timing && !c->shared_device))
-    return false;
-  const int nc = pipe_consumers(c);
+bool shared_launch_ok(const frei_ctx* c) {
+  return c->fast && c->eff && c->shared && !c->use_graph && !c->keys && !c->timing &&
+         !c->shared_device;
+}
+
+// This context's sweeps run chained: a grouped-lane or one-lane (two or more steps in flight)
+// sweep of the contracted table forming its own step records (p.rec_on), fused update (p.fused).
+bool chain_ready(const frei_ctx* c, const SweepPlan& p) {
+  if (!(c->chain && shared_launch_ok(c) && p.rec_on && p.fused)) return false;
   // producer/consumer, four consumers per block; the chained kernel adds the update body's
   // static LDS (4.3 KiB) to the sweep's, which must still fit the CU (deep atmospheres do not)
   // — only on request (FREI_CHAIN=2): chained, its 1024-thread update blocks take 6 µs where
   // the separate update kernel takes 3 (profiles/r03/chain/ab_pipe.txt)
-  if (nc > 0)
-    return c->chain == 2 && nc == 4 &&
+  if (p.NC > 0)
+    return c->chain == 2 && p.NC == 4 &&
            pipe_lds_bytes(4, c->pipe_m, c->nL - 1) + 6 * 1024 <= c->lds_optin;
-  if (group_lanes(c) > 1) return true;      // grouped-lane
+  if (p.Q > 1) return true;      // grouped-lane
   // one-lane (two or more steps in flight): measured neutral to slower at 125k-500k
   // (profiles/r03/chain/ab_onelane.txt), so only on request (FREI_CHAIN=2)
   return c->chain == 2 && c->prefetch_depth != 1;
 }
 
 // Update workgroups of a trailing-update launch (0: not used): the producer/consumer sweep with
-// four consumers, the fused update (one atmosphere, local or P2P exchange), stream launches
-// without per-sweep events (they would time the update with the sweep), not chained, ranks not
-// sharing the device, and — so that they are resident beside the sweep, never waiting behind
-// it — at least two CUs left free by the sweep's one block per CU (eight update blocks at most).
-int tail_blocks(const frei_ctx* c, int nb_sweep) {
-  if (!(c->tail && c->fast && c->eff && c->shared && c->n_atm == 1 && !c->use_graph && !c->keys &&
-        !c->timing && !c->shared_device && !c->chem_on))
-    return 0;
-  if (!(c->fused_update && !c->comm && !(c->nranks > 1 && c->host_ag) &&
-        (2 * (size_t)c->nL + c->tnodes.size()) * sizeof(double) <= 32 * 1024))
-    return 0;
-  if (pipe_consumers(c) != 4 || records_in_sweep(const_cast<frei_ctx*>(c))) return 0;
+// four consumers and the update's records (not p.rec_on), the fused update, one atmosphere, fixed
+// mixing ratios, and — so that they are resident beside the sweep, never waiting behind it — at
+// least two CUs left free by the sweep's one block per CU (eight update blocks at most).
+int tail_blocks(const frei_ctx* c, const SweepPlan& p) {
+  if (!(c->tail && shared_launch_ok(c) && c->n_atm == 1 && !c->chem_on && p.fused)) return 0;
+  if (p.NC != 4 || p.rec_on) return 0;
   if (pipe_tail_lds_bytes(c->nL - 1, (int)c->tnodes.size()) + 6 * 1024 > c->lds_optin) return 0;
-  const int free_cu = c->n_cu - nb_sweep;
+  const int free_cu = c->n_cu - p.nb_run;
   return free_cu >= 2 ? std::min(free_cu, 8) : 0;
+}
+
+// The plan of one sweep.  pending: an update deferred by the sweep before waits for a launch;
+// defer: this sweep may defer its own (both only matter when chained launches apply).
+SweepPlan sweep_plan(const frei_ctx* c, bool pending, bool defer) {
+  SweepPlan p{};
+  const int ns = c->nL - 1;
+  p.S_run = c->eff ? 1 : c->S;
+  p.lds_steps = c->shared;
+  p.pipe_pf = c->pipe_pf;
+  // per-row partials while the one-lane sweep's LDS stays within 48 KiB (3+ blocks per CU)
+  p.red_rows = c->red_rows &&
+               (size_t)16 * ns * 4 * sizeof(double) + (size_t)ns * sizeof(FastStepS) <= 48 * 1024;
+  p.depth = sweep_depth(c, p.S_run);
+  p.pf = sweep_pf(c, c->eff != 0, p.S_run, p.depth);
+  bool any_nan = false;
+  for (int q = 0; q < c->S; ++q) any_nan = any_nan || c->sp[q].has_nan;
+  p.nan_check = any_nan && !c->eff;
+  p.Q = group_lanes(c);
+  // staged partial sums (mode 2): the one-lane sweep with two steps in flight, and the
+  // grouped-lane sweep (two groups in flight)
+  if ((p.Q > 1 || p.depth == 2 || (p.depth == 1 && p.pf == 2)) && c->red_stage &&
+      staged_sums_fit(ns))
+    p.red_rows = 2;
+  p.NW = c->group_waves;
+  p.NC = pipe_consumers(c);
+  p.rec_on = records_in_sweep(c, p.NC);
+  p.fused = fused_ok(c);
+  // (a dry pass only hashes the launches a graph capture would issue: never chained)
+  p.chain = !c->dry && chain_ready(c, p);
+  p.merge = p.chain && pending;
+  p.defer_own = p.chain && defer;
+  p.nb_run = c->nblocks;
+  if (!c->fast) {
+    p.form = kGeneric;
+  } else if (p.NC > 0) {
+    p.form = kPipe;
+    p.nb_run = (int)((c->nlam + 64 * p.NC - 1) / (64 * p.NC));
+    if (!p.merge) p.tail_nT = tail_blocks(c, p);
+  } else if (p.Q > 1) {
+    p.form = kGrouped;
+    p.nb_run = (int)((c->nlam + 64 * p.NW / p.Q - 1) / (64 * p.NW / p.Q));
+  } else if (p.merge) {   // the one-lane contracted sweep, records formed in the block
+    p.form = kOneLane;
+  } else if (c->eff && p.S_run == 1 && !c->shared && !any_nan && p.red_rows == 2 &&
+             lam2_static(c, p.depth, p.pf)) {
+    // two wavelengths per lane: the one-lane contracted sweep on slices that need more than
+    // about one round of one-lane blocks (1280 resident at five waves per SIMD on 256 CUs)
+    p.form = kLam2;
+    p.nb_run = (int)((c->nlam + 2 * kBlock - 1) / (2 * kBlock));
+  } else if (c->tile > 1 && !c->eff && c->chem_on && c->shared && p.red_rows == 2) {
+    p.form = kTiled;   // a chemistry batch, c->tile atmospheres per block
+    p.tile = c->tile;
+  } else {
+    p.form = kOneLane;
+  }
+  // lazy K3: only the two-wavelength sweep with the fused update (which marks the rows it
+  // used) contracts on the way; any other form gets the whole table first
+  p.whole_table = c->fast && !(p.form == kLam2 && p.fused);
+  return p;
 }
 
 // Launch a deferred update on its own (the next sweep cannot take it, or the caller needs its
@@ -857,40 +932,6 @@ uint64_t arg_hash(uint64_t h, const T& x) {
   for (size_t i = 0; i < sizeof(T); ++i) h = (h ^ b[i]) * 1099511628211ull;
   return h;
 }
-
-// The sweep form run_sweep launches for the contracted / per-species tables (c->fast), in one
-// place, so that frei_ctx_path reports what runs.  merge: the launch also runs a deferred update.
-struct FastForm {
-  int S_run, depth, pf, Q, NW, NC, red_rows;
-  bool nan_check, lam2;
-};
-FastForm fast_form(const frei_ctx* c, bool merge) {
-  FastForm m{};
-  const int ns = c->nL - 1;
-  m.S_run = c->eff ? 1 : c->S;
-  // per-row partials while the one-lane sweep's LDS stays within 48 KiB (3+ blocks per CU)
-  m.red_rows = c->red_rows &&
-               (size_t)16 * ns * 4 * sizeof(double) + (size_t)ns * sizeof(FastStepS) <= 48 * 1024;
-  m.depth = sweep_depth(c, m.S_run);
-  m.pf = sweep_pf(c, c->eff != 0, m.S_run, m.depth);
-  m.nan_check = false;
-  for (int q = 0; q < c->S; ++q) m.nan_check = m.nan_check || c->sp[q].has_nan;
-  m.Q = group_lanes(c);
-  // staged partial sums (mode 2): the one-lane sweep with two steps in flight, and the
-  // grouped-lane sweep (two groups in flight)
-  if ((m.Q > 1 || m.depth == 2 || (m.depth == 1 && m.pf == 2)) && c->red_stage &&
-      staged_sums_fit(ns))
-    m.red_rows = 2;
-  m.NW = c->group_waves;
-  m.NC = pipe_consumers(c);
-  // two wavelengths per lane: the one-lane contracted sweep on slices that need more than
-  // about one round of one-lane blocks (1280 resident at five waves per SIMD on 256 CUs)
-  m.lam2 = c->eff && m.S_run == 1 && !c->shared && !m.nan_check && m.Q == 1 && m.NC == 0 &&
-           !merge && m.red_rows == 2 && lam2_static(c, m.depth, m.pf);
-  return m;
-}
-
-bool lam2_form(const frei_ctx* c) { return fast_form(c, false).lam2; }
 
 // Lazy K3: contract every row not contracted yet (any sweep form other than the two-wavelength
 // one, which contracts its masked rows itself, or an update that does not mark them).
@@ -915,24 +956,13 @@ int complete_contraction(frei_ctx* c) {
   return 0;
 }
 
-// One sweep: K1 -> fused reduce + update (+ next setup; P2P exchange inside), or K1 ->
-// reduce -> [RCCL / host all-gather] -> K4/K5 (batched contexts, RCCL, host hook,
-// fused_update 0).  Asynchronous.
-// With c->dry it only appends the hash of every launch's arguments to c->keys and applies
-// the host-side state changes (temperature buffer swap), launching nothing.
-int run_sweep(frei_ctx* c, const SweepOpts& o, bool defer = false) {
-  const int ns = c->nL - 1;
-  // chained: this sweep's launch also runs the deferred update (merge), and this sweep's own
-  // update may be deferred to the next launch (defer_own)
-  const bool chain = !c->dry && chain_ready(c);
-  if (c->has_pend && !chain) TRY(flush_update(c));
-  const bool merge = chain && c->has_pend;
-  const bool defer_own = chain && defer;
-  // the output buffer of this sweep's update: not d_T, and not the merged update's input
-  double* T_next = chain ? free_T(c, merge ? c->pend.su.T : nullptr) : c->d_T_alt;
+// p2p_timeout_s in wall_clock64 ticks (100 MHz): the bound of every device-side wait
+long long timeout_ticks(const frei_ctx* c) { return (long long)(c->p2p_timeout_s * 1e8); }
+
+SweepArgs generic_args(const frei_ctx* c, const SweepOpts& o) {
   SweepArgs a{};
   a.n_lam = c->nlam;
-  a.n_steps = ns;
+  a.n_steps = c->nL - 1;
   a.n_species = c->S;
   a.force = o.force;
   a.live_only = o.live_only;
@@ -948,166 +978,126 @@ int run_sweep(frei_ctx* c, const SweepOpts& o, bool defer = false) {
   a.dtaus = o.dtaus;
   a.part = c->d_part;
   a.conv = c->d_conv;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (c->timing) {
-    e0 = next_event(c);
-    e1 = next_event(c);
-    if (!e0 || !e1) return fail("hipEventCreate failed");
-    HIP_TRY(hipEventRecord(e0, c->stream));
+  return a;
+}
+
+// Arguments of every sweep form on the contracted / per-species tables (c->fast).  T_next: the
+// buffer this sweep's update writes (a deferred update's output starts as kPoisonT).
+FastArgs fast_args(const frei_ctx* c, const SweepOpts& o, const SweepPlan& p, double* T_next) {
+  FastArgs f{};
+  f.n_lam = c->nlam;
+  f.pitch = c->sp[0].stride;
+  f.n_steps = c->nL - 1;
+  f.force = o.force;
+  f.live_only = o.live_only;
+  f.c1 = c->d_c1;
+  f.hcl = c->d_hcl;
+  f.sig = c->d_sig;
+  f.wtr = c->d_wtr;
+  f.ftoa = c->d_ftoa;
+  for (int q = 0; q < kMaxFastS; ++q) f.tab[q] = q < c->S ? c->sp[q].d_tab : nullptr;
+  if (c->eff) f.tab[0] = c->d_eff;
+  if (c->lazy_on && !c->eff_complete) {   // the two-wavelength sweep contracts masked rows
+    for (int q = 0; q < kMaxFastS; ++q) f.ktab[q] = q < c->S ? c->sp[q].d_tab : nullptr;
+    f.kmmr = c->d_mmr;
+    f.kS = c->S;
+    f.kNL = c->nL;
   }
-  int nb_run = c->nblocks;  // partial-sum columns written by this sweep
-  FastArgs tail_f{};        // a trailing-update launch: the sweep's arguments (launched below)
-  int tail_nT = 0;          // its update workgroups (0: not a trailing-update launch)
-  const bool rec_on = c->fast && records_in_sweep(c);
-  // a sweep that reads the update's records after one whose update skipped them (an option or
-  // the tables changed mid-run): write this sweep's records first
-  if (!rec_on && c->rec_skipped && !c->dry) {
-    launch_setup(setup_args(c), o.dir, c->stream, c->n_atm);
-    HIP_TRY(hipGetLastError());
+  f.steps = c->d_fsteps;
+  f.ssteps = c->d_ssteps;
+  f.F_up = c->d_Fu;
+  f.F_down = c->d_Fd;
+  f.dtaus = o.dtaus;
+  f.part = c->d_part;
+  f.conv = c->d_conv;
+  f.bs = atm_stride(c);
+  f.n_atm = c->n_atm;
+  f.unit_mmr = c->eff ? 1 : 0;
+  f.rec_on = p.rec_on;
+  f.min_lds = c->sweep_lds_kb * 1024;
+  if (p.merge) {   // this launch's leading workgroups run the deferred update
+    f.ch_epoch = c->d_epoch;
+    f.ch_val = c->chain_seq;
+    f.ch_can_conv = c->pend.track && c->pend.dir == kAbsorb && c->pend.stop_on_conv;
+    f.ch_timeout = timeout_ticks(c);
+    f.ch_err = c->d_chain_err;
   }
-  c->rec_skipped = false;
-  if (c->fast) {
-    FastArgs f{};
-    f.n_lam = c->nlam;
-    f.pitch = c->sp[0].stride;
-    f.n_steps = ns;
-    f.force = o.force;
-    f.live_only = o.live_only;
-    f.c1 = c->d_c1;
-    f.hcl = c->d_hcl;
-    f.sig = c->d_sig;
-    f.wtr = c->d_wtr;
-    f.ftoa = c->d_ftoa;
-    const FastForm m = fast_form(c, merge);
-    // lazy K3: only the two-wavelength sweep with the fused update (which marks the rows it
-    // used) contracts on the way; any other form gets the whole table first
-    if (c->lazy_on && !c->eff_complete && !c->dry && !(m.lam2 && fused_ok(c)))
-      TRY(complete_contraction(c));
-    const int S_run = m.S_run;
-    for (int q = 0; q < kMaxFastS; ++q) f.tab[q] = q < c->S ? c->sp[q].d_tab : nullptr;
-    if (c->eff) f.tab[0] = c->d_eff;
-    if (c->lazy_on && !c->eff_complete) {   // the two-wavelength sweep contracts masked rows
-      for (int q = 0; q < kMaxFastS; ++q) f.ktab[q] = q < c->S ? c->sp[q].d_tab : nullptr;
-      f.kmmr = c->d_mmr;
-      f.kS = c->S;
-      f.kNL = c->nL;
-    }
-    f.steps = c->d_fsteps;
-    f.ssteps = c->d_ssteps;
-    f.F_up = c->d_Fu;
-    f.F_down = c->d_Fd;
-    f.dtaus = o.dtaus;
-    f.part = c->d_part;
-    f.conv = c->d_conv;
-    f.bs = atm_stride(c);
-    f.n_atm = c->n_atm;
-    f.unit_mmr = c->eff ? 1 : 0;
-    f.rec_on = rec_on ? 1 : 0;
-    f.min_lds = c->sweep_lds_kb * 1024;
-    if (merge) {   // this launch's leading workgroups run the deferred update
-      f.ch_epoch = c->d_epoch;
-      f.ch_val = ++c->chain_seq;
-      f.ch_can_conv = c->pend.track && c->pend.dir == kAbsorb && c->pend.stop_on_conv;
-      f.ch_timeout = (long long)(c->p2p_timeout_s * 1e8);   // wall_clock64: 100 MHz
-      f.ch_err = c->d_chain_err;
-    }
-    if (defer_own) f.poison = T_next;
-    if (f.rec_on) f.rec = setup_args(c);   // T of this sweep: c->d_T now
-    f.red_rows = m.red_rows;
-    const int depth = m.depth, pf = m.pf, Q = m.Q, NW = m.NW, NC = m.NC;
-    const bool nan_check = m.nan_check, lam2 = m.lam2;
-    if (Q > 1) nb_run = (int)((c->nlam + 64 * NW / Q - 1) / (64 * NW / Q));
-    if (NC > 0) nb_run = (int)((c->nlam + 64 * NC - 1) / (64 * NC));
-    if (lam2) nb_run = (int)((c->nlam + 2 * kBlock - 1) / (2 * kBlock));
-    if (c->keys) {
-      uint64_t h = arg_hash(1469598103934665603ull, f);
-      const int cfg[11] = {o.dir, Q, S_run, depth, (nan_check && !c->eff) ? 1 : 0, c->shared,
-                           NC, c->pipe_pf, pf, NW, lam2 ? 1 : 0};
-      c->keys->push_back(arg_hash(h, cfg));
-    }
-    if (c->dry) {
-    } else if (NC > 0 && merge) {
-      UpdateArgs u = c->pend;
-      u.epoch = c->d_epoch;
-      u.epoch_val = c->chain_seq;
-      c->has_pend = false;
-      launch_sweep_pipe_chain(o.dir, c->pipe_pf, f, u, nb_run, c->stream);
-      ++c->n_chained;
-    } else if (NC > 0 && (tail_nT = tail_blocks(c, nb_run)) > 0) {
-      tail_f = f;   // launched with its update (which needs the P2P arguments below)
-    } else if (NC > 0) {
-      launch_sweep_pipe(o.dir, NC, c->pipe_pf, f, nb_run, c->stream);
-    } else if (Q > 1 && merge) {
-      UpdateArgs u = c->pend;
-      u.epoch = c->d_epoch;
-      u.epoch_val = c->chain_seq;
-      c->has_pend = false;
-      launch_sweep_chain(o.dir, Q, NW, f, u, nb_run, c->stream);
-      ++c->n_chained;
-    } else if (Q > 1) {
-      launch_sweep_group(o.dir, Q, NW, f, nb_run, c->stream);
-    } else if (merge) {   // the one-lane contracted sweep, records formed in the block
-      UpdateArgs u = c->pend;
-      u.epoch = c->d_epoch;
-      u.epoch_val = c->chain_seq;
-      c->has_pend = false;
-      launch_sweep_fast_chain(o.dir, depth, pf, f, u, c->nblocks, c->stream);
-      ++c->n_chained;
-    } else if (lam2) {
-      launch_sweep_pair(o.dir, f, nb_run, c->stream);
-    } else if (c->tile > 1 && !c->eff && c->chem_on && c->shared && m.red_rows == 2) {
-      // a chemistry batch, c->tile atmospheres per block
-      launch_sweep_tile(o.dir, S_run, c->tile, f, c->nblocks, c->stream);
-    } else {
-      launch_sweep_fast(o.dir, S_run, depth, pf, nan_check && !c->eff, c->shared != 0, f,
-                        c->nblocks, c->stream);
-    }
-  } else {
-    if (c->keys) c->keys->push_back(arg_hash(arg_hash(1469598103934665603ull, a), o.dir));
-    if (!c->dry) launch_sweep(o.dir, a, c->nblocks, false, c->stream);
+  if (p.defer_own) f.poison = T_next;
+  if (f.rec_on) f.rec = setup_args(c);   // T of this sweep: c->d_T now
+  f.red_rows = p.red_rows;
+  return f;
+}
+
+// The one place a sweep is launched: by the plan's form and modifiers.  A merged launch takes
+// the pending update with it; a trailing-update launch waits for its update (launch_tail).
+void launch_planned(frei_ctx* c, int dir, const SweepPlan& p, const SweepArgs& a,
+                    const FastArgs& f) {
+  UpdateArgs pend{};
+  if (p.merge) {
+    pend = c->pend;
+    pend.epoch = c->d_epoch;
+    pend.epoch_val = c->chain_seq;
+    c->has_pend = false;
+    ++c->n_chained;
   }
-  HIP_TRY(hipGetLastError());
-  if (c->timing) HIP_TRY(hipEventRecord(e1, c->stream));
-  P2PPush push{};
-  P2PWait wait{};
-  if (c->d_mbox && !c->dry) {   // P2P: each rank's sums are pushed and waited for on device
-    const uint64_t seq = ++c->p2p_seq;
-    push.peers = c->d_peers;
-    push.nranks = c->nranks;
-    push.rank = c->rank;
-    push.n = (int64_t)ns * 4;
-    push.seq = seq;
-    wait.mbox = c->d_mbox;
-    wait.nranks = c->nranks;
-    wait.n = push.n;
-    wait.seq = seq;
-    wait.timeout_ticks = (int64_t)(c->p2p_timeout_s * 1e8);   // wall_clock64: 100 MHz
-    wait.err = c->d_comm_err;
-    wait.wait_ticks = c->timing ? c->d_wait_ticks : nullptr;
+  switch (p.form) {
+    case kGeneric:
+      launch_sweep(dir, a, p.nb_run, c->stream);
+      break;
+    case kPipe:
+      if (p.merge) launch_sweep_pipe_chain(dir, p.pipe_pf, f, pend, p.nb_run, c->stream);
+      else if (p.tail_nT == 0) launch_sweep_pipe(dir, p.NC, p.pipe_pf, f, p.nb_run, c->stream);
+      break;
+    case kGrouped:
+      if (p.merge) launch_sweep_chain(dir, p.Q, p.NW, f, pend, p.nb_run, c->stream);
+      else launch_sweep_group(dir, p.Q, p.NW, f, p.nb_run, c->stream);
+      break;
+    case kOneLane:
+      if (p.merge) launch_sweep_fast_chain(dir, p.depth, p.pf, f, pend, p.nb_run, c->stream);
+      else launch_sweep_fast(dir, p.S_run, p.depth, p.pf, p.nan_check != 0, p.lds_steps != 0, f,
+                             p.nb_run, c->stream);
+      break;
+    case kLam2:
+      launch_sweep_pair(dir, f, p.nb_run, c->stream);
+      break;
+    case kTiled:
+      launch_sweep_tile(dir, p.S_run, p.tile, f, p.nb_run, c->stream);
+      break;
   }
-  // one launch for reduce + update: one atmosphere, exchange local or P2P (RCCL and the host
-  // hook need the rank's sums in memory between the two kernels)
-  const bool fused = fused_ok(c);
-  if (!fused && c->dry) {   // not graph-replayable (the check in iterate() sees the marker)
-    if (c->keys) c->keys->push_back(0);
-    return 0;
-  }
-  if (!fused) {
-    const AtmStride bs = atm_stride(c);
-    launch_reduce(c->d_part, nb_run, c->d_Fb, ns * 4, c->d_conv, o.force, c->stream,
-                  c->n_atm, bs.part, bs.fb, c->d_mbox ? &push : nullptr);
-  }
-  HIP_TRY(hipGetLastError());
-  const double* Fb = c->d_Fb;
+}
+
+// P2P: each rank's sums are pushed and waited for on the device
+void p2p_args(frei_ctx* c, P2PPush& push, P2PWait& wait) {
+  const uint64_t seq = ++c->p2p_seq;
+  push.peers = c->d_peers;
+  push.nranks = c->nranks;
+  push.rank = c->rank;
+  push.n = (int64_t)(c->nL - 1) * 4;
+  push.seq = seq;
+  wait.mbox = c->d_mbox;
+  wait.nranks = c->nranks;
+  wait.n = push.n;
+  wait.seq = seq;
+  wait.timeout_ticks = timeout_ticks(c);
+  wait.err = c->d_comm_err;
+  wait.wait_ticks = c->timing ? c->d_wait_ticks : nullptr;
+}
+
+// The rank exchange of the reduced sums through the host hook or RCCL (P2P runs inside the
+// kernels), between HIP events when timing is on.  *Fb: where the update reads the sums.
+int exchange(frei_ctx* c, const double** Fb) {
+  const size_t n = (size_t)(c->nL - 1) * 4;
+  const bool host = c->nranks > 1 && c->host_ag;
+  *Fb = c->d_Fb;
+  if (!host && !c->comm) return 0;
   hipEvent_t x1 = nullptr;
-  if (c->timing && (c->comm || (c->nranks > 1 && c->host_ag))) {   // exchange timing
+  if (c->timing) {
     hipEvent_t x0 = next_event_in(c->xev_pool, c->xev_used);
     x1 = next_event_in(c->xev_pool, c->xev_used);
     if (!x0 || !x1) return fail("hipEventCreate failed");
     HIP_TRY(hipEventRecord(x0, c->stream));
   }
-  if (c->nranks > 1 && c->host_ag) {
-    const size_t n = (size_t)ns * 4;
+  if (host) {
     HIP_TRY(hipMemcpyAsync(c->h_ag, c->d_Fb, n * sizeof(double), hipMemcpyDeviceToHost,
                            c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1115,23 +1105,28 @@ int run_sweep(frei_ctx* c, const SweepOpts& o, bool defer = false) {
       return fail("host all-gather callback failed");
     HIP_TRY(hipMemcpyAsync(c->d_Fb_all, c->h_ag + n, c->nranks * n * sizeof(double),
                            hipMemcpyHostToDevice, c->stream));
-    Fb = c->d_Fb_all;
-  } else if (c->comm) {  // RCCL (also a forced 1-rank communicator, FREI_FORCE_RCCL=1)
+  } else {  // RCCL (also a forced 1-rank communicator, FREI_FORCE_RCCL=1)
     Rccl* r = rccl();
-    if (!r || !c->comm) return fail("RCCL communicator not initialised");
-    int rc = r->allGather(c->d_Fb, c->d_Fb_all, (size_t)ns * 4, kNcclFloat64, c->comm,
-                          c->stream);
+    if (!r) return fail("RCCL communicator not initialised");
+    int rc = r->allGather(c->d_Fb, c->d_Fb_all, n, kNcclFloat64, c->comm, c->stream);
     if (rc != 0)
       return fail(std::string("ncclAllGather: ") + (r->errStr ? r->errStr(rc) : "error"));
-    Fb = c->d_Fb_all;
   }
+  *Fb = c->d_Fb_all;
   if (x1) HIP_TRY(hipEventRecord(x1, c->stream));
+  return 0;
+}
+
+// The update of this sweep (K4/K5, or the fused reduce + update writing T_next).  With the
+// records formed in the sweeps the update writes none for the next one (c->rec_skipped).
+UpdateArgs update_args(frei_ctx* c, const SweepOpts& o, const SweepPlan& p, const P2PPush& push,
+                       const P2PWait& wait, const double* Fb, double* T_next) {
   UpdateArgs u{};
   u.su = setup_args(c);
   u.p2p = wait;
   u.dir = o.dir;
   u.next_dir = o.next_dir;
-  if (c->fast && records_in_sweep(c) && o.next_dir >= 0) {   // the next sweep forms its own
+  if (p.rec_on && o.next_dir >= 0) {   // the next sweep forms its own
     u.next_dir = -1;
     c->rec_skipped = true;
   }
@@ -1158,52 +1153,118 @@ int run_sweep(frei_ctx* c, const SweepOpts& o, bool defer = false) {
   u.conv = c->d_conv;
   // metadata in LDS when the update's whole allocation (the launch's own formula) fits the
   // 64 KiB a workgroup may request
-  const int S_meta = c->eff ? 1 : c->S;
-  u.meta_in_lds = update_lds_bytes(c->nL, (int)c->tnodes.size(), S_meta, true) <=
+  u.meta_in_lds = update_lds_bytes(c->nL, (int)c->tnodes.size(), p.S_run, true) <=
                   std::min<size_t>(c->lds_per_block, 64 * 1024);
-  if (fused) {
+  if (p.fused) {
     u.part = c->d_part;
-    u.nblocks = nb_run;
+    u.nblocks = p.nb_run;
     u.push = push;
     u.T_out = T_next;
     u.done = c->d_done;
-    if (c->keys) c->keys->push_back(arg_hash(1469598103934665603ull, u));
-    if (defer_own) {   // runs at the head of the next sweep's launch, or flush_update
-      c->pend = u;
-      c->has_pend = true;
-    } else if (tail_nT > 0) {   // the sweep and this update in one launch
-      const int64_t need = (int64_t)nb_run * ns * 4;
-      if (c->tpart_n < need) {
-        dfree(c->d_tpart);
-        c->tpart_n = 0;
-        TRY(dalloc(&c->d_tpart, 2 * (size_t)need));
-        c->tpart_n = need;
-        c->tpart_fill = true;
-      }
-      if (c->tpart_fill) {
-        launch_poison(c->d_tpart, 2 * c->tpart_n, c->stream);
-        c->tpart_fill = false;
-        c->tpart_parity = 0;
-      }
-      double* cur = c->d_tpart + c->tpart_parity * c->tpart_n;
-      double* other = c->d_tpart + (1 - c->tpart_parity) * c->tpart_n;
-      c->tpart_parity ^= 1;
-      tail_f.tail_part = cur;
-      u.part = cur;
-      u.poll = 1;
-      u.poll_timeout = (long long)(c->p2p_timeout_s * 1e8);   // wall_clock64: 100 MHz
-      u.poll_err = c->d_chain_err;
-      launch_sweep_pipe_tail(o.dir, c->pipe_pf, tail_f, u, nb_run, tail_nT, other, c->stream);
-      ++c->n_tail;
-    } else if (!c->dry) {
-      launch_update_fused(u, c->stream);
-    }
+  }
+  return u;
+}
+
+// The trailing-update launch: the producer/consumer sweep f and its update u in one launch.
+// The sweep publishes into one of two partial-sum buffers, which the update polls; the update
+// workgroups put the other (the launch before) back to kPoisonT.
+int launch_tail(frei_ctx* c, int dir, const SweepPlan& p, FastArgs f, UpdateArgs u) {
+  const int64_t need = (int64_t)p.nb_run * (c->nL - 1) * 4;
+  if (c->tpart_n < need) {
+    dfree(c->d_tpart);
+    c->tpart_n = 0;
+    TRY(dalloc(&c->d_tpart, 2 * (size_t)need));
+    c->tpart_n = need;
+    c->tpart_fill = true;
+  }
+  if (c->tpart_fill) {
+    launch_poison(c->d_tpart, 2 * c->tpart_n, c->stream);
+    c->tpart_fill = false;
+    c->tpart_parity = 0;
+  }
+  double* cur = c->d_tpart + c->tpart_parity * c->tpart_n;
+  double* other = c->d_tpart + (1 - c->tpart_parity) * c->tpart_n;
+  c->tpart_parity ^= 1;
+  f.tail_part = cur;
+  u.part = cur;
+  u.poll = 1;
+  u.poll_timeout = timeout_ticks(c);
+  u.poll_err = c->d_chain_err;
+  launch_sweep_pipe_tail(dir, p.pipe_pf, f, u, p.nb_run, p.tail_nT, other, c->stream);
+  ++c->n_tail;
+  return 0;
+}
+
+// One sweep: K1 -> fused reduce + update (+ next setup; P2P exchange inside), or K1 ->
+// reduce -> [RCCL / host all-gather] -> K4/K5 (batched contexts, RCCL, host hook,
+// fused_update 0).  Asynchronous.
+//   plan -> setup / contraction the plan asks for -> sweep launch -> exchange ->
+//   update launched, deferred (chained) or trailing the sweep -> rotate_T
+// With c->dry it only appends the hash of every launch's arguments to c->keys and applies
+// the host-side state changes (temperature buffer swap), launching nothing.
+int run_sweep(frei_ctx* c, const SweepOpts& o, bool defer = false) {
+  const SweepPlan p = sweep_plan(c, c->has_pend, defer);
+  if (c->has_pend && !p.merge) TRY(flush_update(c));   // (not chained: the next cannot take it)
+  // the output buffer of this sweep's update: not d_T, and not the merged update's input
+  double* T_next = p.chain ? free_T(c, p.merge ? c->pend.su.T : nullptr) : c->d_T_alt;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (c->timing) {
+    e0 = next_event(c);
+    e1 = next_event(c);
+    if (!e0 || !e1) return fail("hipEventCreate failed");
+    HIP_TRY(hipEventRecord(e0, c->stream));
+  }
+  // a sweep that reads the update's records after one whose update skipped them (an option or
+  // the tables changed mid-run): write this sweep's records first
+  if (!p.rec_on && c->rec_skipped && !c->dry) {
+    launch_setup(setup_args(c), o.dir, c->stream, c->n_atm);
     HIP_TRY(hipGetLastError());
-    rotate_T(c, T_next);
+  }
+  c->rec_skipped = false;
+  if (p.whole_table && c->lazy_on && !c->eff_complete && !c->dry) TRY(complete_contraction(c));
+  if (p.merge) ++c->chain_seq;
+  const SweepArgs a = generic_args(c, o);
+  const FastArgs f = c->fast ? fast_args(c, o, p, T_next) : FastArgs{};
+  if (c->keys) {   // any change of the plan or of the arguments re-captures
+    const uint64_t seed = 1469598103934665603ull;
+    const uint64_t h = c->fast ? arg_hash(seed, f) : arg_hash(seed, a);
+    c->keys->push_back(arg_hash(arg_hash(h, p), o.dir));
+  }
+  if (!c->dry) launch_planned(c, o.dir, p, a, f);
+  HIP_TRY(hipGetLastError());
+  if (c->timing) HIP_TRY(hipEventRecord(e1, c->stream));
+  P2PPush push{};
+  P2PWait wait{};
+  if (c->d_mbox && !c->dry) p2p_args(c, push, wait);
+  if (!p.fused && c->dry) {   // not graph-replayable (the check in iterate() sees the marker)
+    if (c->keys) c->keys->push_back(0);
     return 0;
   }
-  launch_update(u, c->stream, c->n_atm);
+  if (!p.fused) {
+    const AtmStride bs = atm_stride(c);
+    launch_reduce(c->d_part, p.nb_run, c->d_Fb, (c->nL - 1) * 4, c->d_conv, o.force, c->stream,
+                  c->n_atm, bs.part, bs.fb, c->d_mbox ? &push : nullptr);
+  }
   HIP_TRY(hipGetLastError());
+  const double* Fb = nullptr;
+  TRY(exchange(c, &Fb));
+  const UpdateArgs u = update_args(c, o, p, push, wait, Fb, T_next);
+  if (!p.fused) {
+    launch_update(u, c->stream, c->n_atm);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+  if (c->keys) c->keys->push_back(arg_hash(1469598103934665603ull, u));
+  if (p.defer_own) {   // runs at the head of the next sweep's launch, or flush_update
+    c->pend = u;
+    c->has_pend = true;
+  } else if (p.tail_nT > 0) {
+    TRY(launch_tail(c, o.dir, p, f, u));
+  } else if (!c->dry) {
+    launch_update_fused(u, c->stream);
+  }
+  HIP_TRY(hipGetLastError());
+  rotate_T(c, T_next);
   return 0;
 }
 
@@ -1233,7 +1294,7 @@ int ensure_hist(frei_ctx* c, int cap) {
 }
 
 // Per-atmosphere strides of a batched context (all zero for one atmosphere).
-AtmStride atm_stride(frei_ctx* c) {
+AtmStride atm_stride(const frei_ctx* c) {
   AtmStride b{};
   if (c->n_atm <= 1) return b;
   const int64_t nL = c->nL, ns = nL - 1;
@@ -2643,19 +2704,15 @@ int frei_ctx_path(frei_ctx* c, int* flags) {
   TRY(build_meta(c));
   int nan = 0;
   for (const auto& q : c->sp) nan = nan || q.has_nan;
-  // the form run_sweep launches: a loop's sweeps after the first merge a deferred update when
-  // chained launches apply
-  const FastForm m = fast_form(c, chain_ready(c));
-  const int Q = m.Q, NC = m.NC;
-  const bool lam2 = c->fast && m.lam2;
+  // the plan run_sweep launches from, for a loop's sweeps after the first: they merge a deferred
+  // update when chained launches apply
+  const SweepPlan p = sweep_plan(c, true, false);
   const int tile = (c->fast && !c->eff) ? c->tile : 0;   // a chemistry batch's sweep
   *flags = (tile << 12) |
            (c->fast ? 1 : 0) | (c->fast && c->shared && tile <= 1 ? 2 : 0) | (c->eff ? 4 : 0) |
-           (nan ? 8 : 0) | (NC == 0 && Q == 2 ? 16 : 0) | (NC == 0 && Q == 4 ? 32 : 0) |
-           (NC << 6) | (lam2 ? 512 : 0) |
-           (c->fast && NC > 0 && !chain_ready(c) && tail_blocks(c, (int)((c->nlam + 255) / 256)) > 0
-                ? 1024 : 0) |
-           (c->lazy_on ? 2048 : 0);
+           (nan ? 8 : 0) | (p.form == kGrouped && p.Q == 2 ? 16 : 0) |
+           (p.form == kGrouped && p.Q == 4 ? 32 : 0) | (p.NC << 6) |
+           (p.form == kLam2 ? 512 : 0) | (p.tail_nT > 0 ? 1024 : 0) | (c->lazy_on ? 2048 : 0);
   return 0;
 }
 
