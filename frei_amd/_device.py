@@ -1,5 +1,5 @@
 """What the device-side objects share (StellarSpectra, Instrument, CrossCorrelator, Broadening,
-OrbitStack):
+OrbitStack, ModelGrid):
 the handle's lifecycle and the kernel timing (:class:`DeviceObject`), the choice between spectra
 resident on the device and a host array (:func:`resident_or_host`), and the argument checks of
 the calls that take a library, a ``select`` and numbers per atmosphere.  A new post-processing
@@ -60,12 +60,21 @@ class DeviceObject:
         self._calls += 1
 
 
+def kept_suffix(x):
+    """The suffix of the C entry points that read ``x`` where it lies on the device: ``"_brd"``
+    for a :class:`~frei_amd.broaden.BroadenedSpectra`, ``"_itp"`` for an
+    :class:`~frei_amd.modelgrid.InterpolatedSpectra`; None for anything else."""
+    return getattr(x, "suffix", None) if hasattr(x, "owner") and hasattr(x, "serial") else None
+
+
 def resident_or_host(x, engine, n_lam, consumer):
-    """Where a call's spectra come from -> ``(x2d, ctx, brd, n_atm, single, unit)``, one of the
-    first three set: a :class:`~frei_amd.broaden.BroadenedSpectra` as ``x`` (its Broadening's
-    handle, after the staleness check), ``x=None`` with ``engine=`` (the engine's context), or
-    a host array [n_lam] or [n_atm][n_lam] (a Quantity's numbers as they are, its unit in
-    ``unit``).  ``consumer`` is ``(noun with its article, what may straddle slices)``."""
+    """Where a call's spectra come from -> ``(x2d, ctx, kept, n_atm, single, unit)``, one of the
+    first three set: spectra kept on the device as ``x`` — a
+    :class:`~frei_amd.broaden.BroadenedSpectra` or an
+    :class:`~frei_amd.modelgrid.InterpolatedSpectra`, told apart by :func:`kept_suffix` — (their
+    owner's handle, after the staleness check), ``x=None`` with ``engine=`` (the engine's
+    context), or a host array [n_lam] or [n_atm][n_lam] (a Quantity's numbers as they are, its
+    unit in ``unit``).  ``consumer`` is ``(noun with its article, what may straddle slices)``."""
     if hasattr(x, "owner") and hasattr(x, "serial"):
         return None, None, x.handle(), x.n_atm, x.single, None
     if x is None:

@@ -146,6 +146,20 @@ SIGNATURES = {
                                         ctypes.c_double, _dp, _dp, ctypes.c_double, _dp, _dp,
                                         ctypes.c_int, _ip, _dp]),
     "frei_stack_destroy": (ctypes.c_int, [_vp]),
+    "frei_itp_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _i64, ctypes.c_int]),
+    "frei_itp_set_nodes": (ctypes.c_int, [_vp, _vp, _vp, _dp]),
+    "frei_itp_apply": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(ctypes.c_int32), _dp, ctypes.c_int, _dp,
+                                      ctypes.c_int, _ip, _dp]),
+    "frei_itp_destroy": (ctypes.c_int, [_vp]),
+    "frei_ccf_apply_itp": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int32), _dp, _dp,
+                                          ctypes.c_int, _dp, _dp, _dp, _ip, _dp]),
+    "frei_obs_apply_itp": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int32), _dp, _dp, _dp,
+                                          ctypes.c_int, _dp, _dp, _ip, _dp]),
+    "frei_brd_apply_itp": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _dp,
+                                          ctypes.c_int, _ip, _dp]),
 }
 
 _lib = None

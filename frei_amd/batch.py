@@ -427,6 +427,22 @@ class BatchResult(list):
                                R_star=R_star, offset=offset, broadening=broadening, keep=keep,
                                **kw)
 
+    def model_grid(self, axes, broadening=None):
+        """A :class:`~frei_amd.modelgrid.ModelGrid` (K15) whose nodes are the spectra the run
+        left on the device, copied device to device without a host copy: ``axes`` are the
+        sweep's parameter axes (1 to 4 strictly ascending arrays whose lengths multiply to the
+        number of atmospheres), atmosphere ``m`` the node of C-order index ``m`` over them (the
+        last axis fastest).  With ``broadening`` (:class:`~frei_amd.broaden.Broadening`, K13) the
+        nodes are broadened first, resident to resident.  Interpolation is linear and its weights
+        do not depend on wavelength, so broadening the nodes once equals broadening every
+        interpolated query (up to rounding).  The grid owns its copy: it outlives :meth:`close`."""
+        from .modelgrid import ModelGrid
+        eng = self.engine
+        if broadening is not None:
+            kept = broadening.apply(engine=eng, keep=True)
+            return ModelGrid(axes, eng.lam_um, spectra=kept, device=eng.device)
+        return ModelGrid(axes, eng.lam_um, engine=eng, device=eng.device)
+
     def close(self):
         self.engine.close()
 

@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
-from ._device import DeviceObject, i32ptr, resident_or_host
+from ._device import DeviceObject, i32ptr, kept_suffix, resident_or_host
 from .crosscorr import C_KMS
 from .units import value
 
@@ -186,6 +186,8 @@ class BroadenedSpectra:
     to ``CrossCorrelator.correlate`` or ``Instrument.apply``.  It goes stale at the owner's next
     ``apply`` or ``release``; using a stale one raises."""
 
+    suffix = "_brd"     # the C entry points that read it: frei_*_apply_brd
+
     def __init__(self, owner, serial, n_atm, single):
         self.owner, self.serial, self.n_atm, self.single = owner, serial, n_atm, single
 
@@ -266,20 +268,27 @@ class Broadening(DeviceObject):
         """``x`` ([n_lam] or [n_atm][n_lam]) broadened -> an array of the same shape (a
         Quantity's numbers as they are, its unit put back).  ``x=None`` with ``engine=`` (an
         Engine or BatchEngine on the whole axis) takes the emergent spectra resident in the
-        engine's flux state.  ``form`` 0 picks the kernel, a member of ``FORMS`` forces it
+        engine's flux state; an :class:`~frei_amd.modelgrid.InterpolatedSpectra` as ``x`` takes
+        what ``ModelGrid.interpolate(keep=True)`` left on the device.  ``form`` 0 picks the
+        kernel, a member of ``FORMS`` forces it
         (``form_used`` records the choice).  ``keep=True`` leaves the result on the device and
         returns a :class:`BroadenedSpectra` for ``CrossCorrelator.correlate`` or
         ``Instrument.apply``; nothing is copied back."""
-        x, ctx, brd, n_atm, single, unit = resident_or_host(
-            x, engine, self.n_lam, ("a broadener", "a window"))
-        if brd is not None:
+        kept = kept_suffix(x)
+        if kept == "_brd":
             raise TypeError("a BroadenedSpectra cannot be broadened again: pass an array")
+        x, ctx, itp, n_atm, single, unit = resident_or_host(
+            x, engine, self.n_lam, ("a broadener", "a window"))
         out = None if keep else np.empty((n_atm, self.n_lam))
         used, ms = ctypes.c_int(0), ctypes.c_double(0.0)
         handle = self.handle()
         self._serial += 1                          # whatever was kept ends with this call
-        N.check(N.lib().frei_brd_apply(handle, ctx, N.dptr(x), n_atm, int(form), N.dptr(out),
-                                       1 if keep else 0, ctypes.byref(used), ctypes.byref(ms)))
+        tail = (n_atm, int(form), N.dptr(out), 1 if keep else 0, ctypes.byref(used),
+                ctypes.byref(ms))
+        if itp is not None:
+            N.check(N.lib().frei_brd_apply_itp(handle, itp, *tail))
+        else:
+            N.check(N.lib().frei_brd_apply(handle, ctx, N.dptr(x), *tail))
         self._record(used, ms)
         if keep:
             return BroadenedSpectra(self, self._serial, n_atm, single)

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _native as N
 from ._device import (DeviceObject, broadened_source, i32ptr, library_rows, per_atmosphere,
-                      resident_or_host, select_rows, unknown_kind)
+                      kept_suffix, resident_or_host, select_rows, unknown_kind)
 from .units import value
 
 __all__ = ["CrossCorrelator", "CrossCorrelation", "KeptSums", "kp_vsys_map", "FORMS",
@@ -194,7 +194,9 @@ class CrossCorrelator(DeviceObject):
         numbers per atmosphere; an absent one drops its operation.  ``x=None`` with ``engine=``
         (an Engine or BatchEngine on the whole axis) takes the emergent spectra resident in the
         engine's flux state; a :class:`~frei_amd.broaden.BroadenedSpectra` as ``x`` takes what
-        ``Broadening.apply(keep=True)`` left on the device.  ``form`` 0 picks the kernel, a
+        ``Broadening.apply(keep=True)`` left on the device, an
+        :class:`~frei_amd.modelgrid.InterpolatedSpectra` what
+        ``ModelGrid.interpolate(keep=True)`` left there.  ``form`` 0 picks the kernel, a
         member of ``FORMS`` forces it (``form_used`` records the choice).  ``want`` names the
         sums to compute (``"sfg"``, ``"sg"``, ``"sgg"``; the others are None and cost
         nothing).  ``keep=True`` also leaves the computed sums on the device (the result's
@@ -204,6 +206,7 @@ class CrossCorrelator(DeviceObject):
         want = (want,) if isinstance(want, str) else tuple(want)
         if any(k not in _SUMS for k in want):
             raise ValueError(f"want holds names other than {_SUMS}: {want}")
+        kept = kept_suffix(x)
         x, ctx, brd, n_atm, single, _ = resident_or_host(
             x, engine, self.n_lam, ("a correlator", "a pixel's bracket"))
         den = library_rows(den, "den", self.n_lam)
@@ -224,7 +227,7 @@ class CrossCorrelator(DeviceObject):
             N.check(N.lib().frei_ccf_keep(handle, 1 if keep else 0))
             self._keep_on = bool(keep)
         if brd is not None:
-            N.check(N.lib().frei_ccf_apply_brd(handle, brd, n_atm, *tail))
+            N.check(getattr(N.lib(), "frei_ccf_apply" + kept)(handle, brd, n_atm, *tail))
         else:
             N.check(N.lib().frei_ccf_apply(handle, ctx, N.dptr(x), n_atm, *tail))
         self._record(used, ms)

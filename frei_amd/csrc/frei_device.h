@@ -551,6 +551,17 @@ struct BrdRows {
 };
 int brd_kept_rows(frei_brd* b, BrdRows* out);
 }  // namespace frei
+struct frei_itp;
+namespace frei {
+// K15 (frei_interp.hip): what the interpolator's last apply kept, [n_query][n_lam] doubles back
+// to back on `device`, complete (its stream was synchronised); rows is null with nothing kept.
+struct ItpRows {
+  const double* rows;
+  int64_t n_lam;
+  int n_query, device;
+};
+int itp_kept_rows(frei_itp* p, ItpRows* out);
+}  // namespace frei
 struct frei_ccf;
 namespace frei {
 // K12 (frei_crosscorr.hip): what the correlator's last apply kept in keep mode — sfg

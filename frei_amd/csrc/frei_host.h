@@ -158,22 +158,37 @@ class DeviceCall {
   std::vector<void*> kept_;
 };
 
-// Where a consumer (an instrument, a correlator, a broadener) reads its spectra
-// x[n_atm][n_lam]: the caller's host array (rows stays null: the caller uploads x), a context's
-// emergent rows in place, or what a broadener kept (K13).  `noun` is the consumer in the
-// messages, `entry` its C entry point.
+// Where a consumer (an instrument, a correlator, a broadener, an interpolator's library) reads
+// its spectra x[n_atm][n_lam]: the caller's host array (rows stays null: the caller uploads x), a
+// context's emergent rows in place, what a broadener kept (K13) or what an interpolator kept
+// (K15: its queries are the atmospheres).  `noun` is the consumer in the messages, `entry` its C
+// entry point.
 struct SpectrumRows {
   const double* rows;
   int64_t stride;
   hipStream_t stream;
 };
 
-inline int spectrum_rows(const double* x, frei_ctx* ctx, frei_brd* brd, int n_atm, int64_t n_lam,
-                         int device, hipStream_t own, const std::string& noun,
+inline int spectrum_rows(const double* x, frei_ctx* ctx, frei_brd* brd, frei_itp* itp, int n_atm,
+                         int64_t n_lam, int device, hipStream_t own, const std::string& noun,
                          const std::string& entry, SpectrumRows* out) {
   *out = SpectrumRows{nullptr, n_lam, own};
   const std::string N = std::to_string(n_atm);
-  if (brd) {
+  if (itp) {
+    const std::string e = entry + "_itp: ";
+    ItpRows ir{};
+    TRY(itp_kept_rows(itp, &ir));
+    if (!ir.rows) return set_error(e + "the interpolator holds nothing kept (apply with keep)");
+    if (ir.n_lam != n_lam)
+      return set_error(e + "the interpolator's n_lam = " + std::to_string(ir.n_lam) +
+                       " is not the " + noun + "'s " + std::to_string(n_lam));
+    if (ir.n_query != n_atm)
+      return set_error(e + "the interpolator keeps " + std::to_string(ir.n_query) +
+                       " queries, not n_atm = " + N);
+    if (ir.device != device)
+      return set_error(e + "interpolator and " + noun + " live on different devices");
+    out->rows = ir.rows;
+  } else if (brd) {
     const std::string e = entry + "_brd: ";
     BrdRows br{};
     TRY(brd_kept_rows(brd, &br));

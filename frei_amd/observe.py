@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _native as N
 from ._device import (DeviceObject, broadened_source, i32ptr, library_rows, per_atmosphere,
-                      resident_or_host, select_rows, unknown_kind)
+                      kept_suffix, resident_or_host, select_rows, unknown_kind)
 from .engine import trapz_weights
 from .transit import default_radius
 from .twostream import BB
@@ -200,9 +200,12 @@ class Instrument(DeviceObject):
         factor per atmosphere.  ``x=None`` with ``engine=`` (an Engine or BatchEngine on the
         whole axis) takes the emergent spectra resident in the engine's flux state; a
         :class:`~frei_amd.broaden.BroadenedSpectra` as ``x`` takes what
-        ``Broadening.apply(keep=True)`` left on the device.  ``form``
+        ``Broadening.apply(keep=True)`` left on the device, an
+        :class:`~frei_amd.modelgrid.InterpolatedSpectra` what
+        ``ModelGrid.interpolate(keep=True)`` left there (its queries are the atmospheres).  ``form``
         0 picks the kernel from the points per channel, 1 forces one lane per channel, 2 one
         group of lanes per channel (``form_used`` records the choice)."""
+        kept = kept_suffix(x)
         x, ctx, brd, n_atm, single, _ = resident_or_host(
             x, engine, self.n_lam, ("an instrument", "a channel"))
         num = library_rows(num, "num", self.n_lam)
@@ -229,7 +232,7 @@ class Instrument(DeviceObject):
                 N.dptr(sigma), int(form), N.dptr(obs), N.dptr(chi2), ctypes.byref(used),
                 ctypes.byref(ms))
         if brd is not None:
-            N.check(N.lib().frei_obs_apply_brd(self.handle(), brd, n_atm, *tail))
+            N.check(getattr(N.lib(), "frei_obs_apply" + kept)(self.handle(), brd, n_atm, *tail))
         else:
             N.check(N.lib().frei_obs_apply(self.handle(), ctx, N.dptr(x), n_atm, *tail))
         self._record(used, ms)
@@ -245,8 +248,9 @@ class Instrument(DeviceObject):
         radii in cm or Quantities, scalars or one per atmosphere."""
         ratio = np.asarray(value(R_p, "cm")) / np.asarray(value(R_star, "cm"))
         F_star = None if F_star is None else value(F_star, FLUX)
-        return self.apply(value(F_planet, FLUX), den=F_star, select=select,
-                          scale=ratio * ratio, **kw)
+        if kept_suffix(F_planet) is None:       # spectra kept on the device pass as they are
+            F_planet = value(F_planet, FLUX)
+        return self.apply(F_planet, den=F_star, select=select, scale=ratio * ratio, **kw)
 
     def transit(self, depth, F_star=None, select=None, **kw):
         """Band-averaged transit depths, weighted by the stellar flux ``F_star`` (a library

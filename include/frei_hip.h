@@ -790,6 +790,108 @@ int frei_stack_apply(frei_stack* s, frei_ccf* kept, int n_atm, const double* sfg
                      double* values, int form, int* form_used, double* kernel_ms);
 int frei_stack_destroy(frei_stack* s);
 
+/*
+ * Model-grid interpolation (K15): spectra at arbitrary points between the node spectra of a
+ * grid sweep, as weighted sums of a few nodes each, formed and kept on the device.  The
+ * reference has no counterpart; this is the definition.
+ * An interpolator on `device` holds a library of node spectra X[n_node][n_lam] in a buffer of its
+ * own.  frei_itp_create checks n_lam >= 1, n_node >= 1 and n_lam / 512 <= 65535 (the launch grid)
+ * and touches no device; the buffer is allocated by the first frei_itp_set_nodes.
+ */
+#define FREI_ITP_MAX_CORNERS 16
+typedef struct frei_itp frei_itp;
+int frei_itp_create(frei_itp** out, int device, int64_t n_lam, int n_node);
+/*
+ * Fill the library from one of the three sources of spectra: x, a host array [n_node][n_lam]; or
+ * x NULL with ctx, the emergent row F_up[n_layers - 1] of every atmosphere of the context, copied
+ * where it lies on the context's stream behind the work that wrote it, honouring the row stride
+ * of the flux state; or x and ctx NULL with brd, what frei_brd_apply kept.  The context or the
+ * broadener must hold n_node rows of n_lam points on the interpolator's device.  The rows are
+ * copied: the source may be reused or closed once the call returns.  Setting nodes again replaces
+ * the library; whatever frei_itp_apply kept ends with any frei_itp_set_nodes whose arguments are
+ * accepted, successful or not, and after a failed one no nodes are set.
+ * Errors: a null handle, all three sources null, a source of another shape or device, a broadener
+ * with nothing kept.
+ */
+int frei_itp_set_nodes(frei_itp* itp, frei_ctx* ctx, frei_brd* brd, const double* x);
+/*
+ * Interpolate n_query spectra from the plan idx[n_query][n_corner] (int32, 0 <= idx < n_node)
+ * and w[n_query][n_corner] (fp64), 1 <= n_corner <= FREI_ITP_MAX_CORNERS.  Per query q and
+ * wavelength i, by exactly these IEEE operations, the corners in ascending c, one multiply and
+ * one add per term, never contracted (NumPy's acc + w * x):
+ *   acc = w[q][0] * X[idx[q][0]][i]
+ *   acc = acc + w[q][c] * X[idx[q][c]][i]            for c = 1 .. n_corner - 1
+ *   out[q][i] = acc
+ * The device normalises, clamps and transforms nothing: what the weights mean (multilinear
+ * corners, simplices, a barycentric scheme) is the caller's business.  A node may appear in
+ * several corners of a query.  Nothing in w or X is checked.
+ * out[n_query][n_lam] receives the result; it may be NULL when keep is set.  The result is formed
+ * in a device buffer the handle owns, reused from call to call and grown when a call needs more.
+ * With keep != 0 the result stays valid there until the next frei_itp_apply (kept or
+ * not, successful or not once its arguments are accepted), frei_itp_set_nodes (likewise) or
+ * frei_itp_destroy; frei_ccf_apply_itp, frei_obs_apply_itp and frei_brd_apply_itp read it there.
+ * Two forms give the same bits (the operations per output above do not depend on the form):
+ *   form 1 (gather): one lane owns two consecutive outputs (q, i), (q, i + 1) and reads its
+ *     corners' node values from global memory 16 bytes at a time (the library's rows are padded
+ *     to a 16-byte-aligned pitch).  The blocks of one tile of 512 wavelengths, over all queries,
+ *     are consecutive in the grid, so the tile's slab of X (n_node x 4 KiB) is read from L2.
+ *     Traffic at L2: n_corner reads per output.
+ *   form 2 (LDS-staged): one workgroup of FREI_ITP_LDS_WAVES waves owns a tile of T consecutive
+ *     wavelengths, stages X[0 .. n_node)[tile] in LDS once and runs over every query, wave v
+ *     taking the queries v, v + FREI_ITP_LDS_WAVES, ...: idx and w of a query are uniform in
+ *     its wave, lane l reads the LDS doubles at l + 64 k of a node's row (consecutive 8-byte
+ *     addresses, conflict-free) and a row of out is written in runs of a whole tile.  HBM
+ *     traffic: the library once plus the output once, whatever n_corner is.  A query's corners
+ *     alone are multiplied in: a node it does not list never enters its sum.
+ *     Tile-width rule: T is the widest of 256, 128 and 64 with n_node * T * 8 bytes <=
+ *     FREI_ITP_LDS_BYTES (the CU's whole LDS, one workgroup per CU beyond half of it): 256 up to
+ *     80 nodes, 128 up to 160, 64 up to FREI_ITP_LDS_MAX_NODES = 320.  A taller library is an
+ *     error for form 2.
+ *   form 0 takes form 2 where it fits, the axis gives at least 256 tiles (one workgroup per CU;
+ *     fewer leave CUs idle whatever the query count), n_query >= FREI_ITP_LDS_FROM_QUERIES = 32
+ *     and n_corner >= FREI_ITP_LDS_FROM_CORNERS = 12, form 1 otherwise: the crossover measured
+ *     on MI355X at 256 nodes x 100k wavelengths (tools/interp_probe.py,
+ *     profiles/r15/interp/README.md): at 16 corners form 2 wins from 64 queries on, at 8 the
+ *     forms tie within the run-to-run spread, at 2 corners and for a single query form 1 wins;
+ *     the thresholds are the midpoints of the timed neighbours (8 and 16 corners, 1 and 64
+ *     queries).  *form_used receives the form that ran.
+ * No atomics: results are bitwise the same from call to call and between the forms, row q of a
+ * call is bitwise the call on that query alone, and an output does not change when other queries
+ * or unused nodes are added.  A NaN or inf in X[n][i] reaches exactly the outputs (q, i) of the
+ * queries that list node n in any corner, whatever its weight (0 * NaN also counts), and no other
+ * wavelength or query, in both forms.
+ * *form_used and *kernel_ms (HIP events around the kernel only) may be NULL.  Errors, all found on
+ * the host before any device call, naming the first offending index (the handle stays usable): a
+ * null handle; n_query < 1; n_corner outside its range; idx or w null; out null without keep; a
+ * form outside 0 .. 2; an idx outside [0, n_node); form 2 with a library too tall; no nodes set.
+ */
+#define FREI_ITP_LDS_BYTES 163840
+#define FREI_ITP_LDS_WAVES 16
+#define FREI_ITP_LDS_MAX_NODES 320
+#define FREI_ITP_LDS_FROM_QUERIES 32
+#define FREI_ITP_LDS_FROM_CORNERS 12
+int frei_itp_apply(frei_itp* itp, int n_query, int n_corner, const int32_t* idx, const double* w,
+                   int form, double* out, int keep, int* form_used, double* kernel_ms);
+int frei_itp_destroy(frei_itp* itp);
+/*
+ * frei_ccf_apply, frei_obs_apply and frei_brd_apply with the result `src` kept (frei_itp_apply
+ * with keep) as their x: a fourth source beside the host array, the context and the broadener,
+ * read where it lies.  The queries play the role of the atmospheres (n_atm = n_query): select,
+ * scale, offset and den are per query.  The other arguments and the results are those of the
+ * plain calls, bitwise what they give for a host copy of the same numbers.  Errors: a null
+ * interpolator, one with nothing kept, or one of another n_lam, n_query or device.
+ */
+int frei_ccf_apply_itp(frei_ccf* c, frei_itp* src, int n_atm, const double* den, int n_lib,
+                       const int32_t* select, const double* scale, const double* offset,
+                       int form, double* sfg, double* sg, double* sgg, int* form_used,
+                       double* kernel_ms);
+int frei_obs_apply_itp(frei_obs* o, frei_itp* src, int n_atm, const double* num,
+                       const double* den, int n_lib, const int32_t* select, const double* scale,
+                       const double* data, const double* sigma, int form, double* obs,
+                       double* chi2, int* form_used, double* kernel_ms);
+int frei_brd_apply_itp(frei_brd* b, frei_itp* src, int n_atm, int form, double* out, int keep,
+                       int* form_used, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
