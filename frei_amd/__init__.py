@@ -16,6 +16,7 @@ from .broaden import BroadenedSpectra, Broadening, BroadeningKernel
 from .emergent import gauss_angles
 from .stack import OrbitStack
 from .modelgrid import InterpolatedSpectra, ModelGrid
+from .phasecurve import PhaseCurve, PhaseSpectra, lonlat_cells
 from .engine import Engine, balanced_edges, partition, trapz_weights
 from .observe import Instrument
 from .opacity import (OpacityTable, SeparableTable, binned_opacity, kappa,
@@ -36,4 +37,5 @@ __all__ = ["Planet", "Grid", "Spectrum", "effective_temperature", "wavelength_gr
            "batched_emission_spectra", "ChemistryTable", "BatchRecord", "BatchResult",
            "StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum",
            "level_radii", "Instrument", "gauss_angles", "CrossCorrelator", "CrossCorrelation",
-           "kp_vsys_map", "OrbitStack", "ModelGrid", "InterpolatedSpectra"]
+           "kp_vsys_map", "OrbitStack", "ModelGrid", "InterpolatedSpectra", "PhaseCurve",
+           "PhaseSpectra", "lonlat_cells"]

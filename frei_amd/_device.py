@@ -1,5 +1,5 @@
 """What the device-side objects share (StellarSpectra, Instrument, CrossCorrelator, Broadening,
-OrbitStack, ModelGrid):
+OrbitStack, ModelGrid, PhaseCurve):
 the handle's lifecycle and the kernel timing (:class:`DeviceObject`), the choice between spectra
 resident on the device and a host array (:func:`resident_or_host`), and the argument checks of
 the calls that take a library, a ``select`` and numbers per atmosphere.  A new post-processing
@@ -63,15 +63,17 @@ class DeviceObject:
 def kept_suffix(x):
     """The suffix of the C entry points that read ``x`` where it lies on the device: ``"_brd"``
     for a :class:`~frei_amd.broaden.BroadenedSpectra`, ``"_itp"`` for an
-    :class:`~frei_amd.modelgrid.InterpolatedSpectra`; None for anything else."""
+    :class:`~frei_amd.modelgrid.InterpolatedSpectra`, ``"_phs"`` for a
+    :class:`~frei_amd.phasecurve.PhaseSpectra`; None for anything else."""
     return getattr(x, "suffix", None) if hasattr(x, "owner") and hasattr(x, "serial") else None
 
 
 def resident_or_host(x, engine, n_lam, consumer):
     """Where a call's spectra come from -> ``(x2d, ctx, kept, n_atm, single, unit)``, one of the
     first three set: spectra kept on the device as ``x`` — a
-    :class:`~frei_amd.broaden.BroadenedSpectra` or an
-    :class:`~frei_amd.modelgrid.InterpolatedSpectra`, told apart by :func:`kept_suffix` — (their
+    :class:`~frei_amd.broaden.BroadenedSpectra`, an
+    :class:`~frei_amd.modelgrid.InterpolatedSpectra` or a
+    :class:`~frei_amd.phasecurve.PhaseSpectra`, told apart by :func:`kept_suffix` — (their
     owner's handle, after the staleness check), ``x=None`` with ``engine=`` (the engine's
     context), or a host array [n_lam] or [n_atm][n_lam] (a Quantity's numbers as they are, its
     unit in ``unit``).  ``consumer`` is ``(noun with its article, what may straddle slices)``."""

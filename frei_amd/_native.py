@@ -160,6 +160,19 @@ SIGNATURES = {
                                           ctypes.c_int, _dp, _dp, _ip, _dp]),
     "frei_brd_apply_itp": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _dp,
                                           ctypes.c_int, _ip, _dp]),
+    "frei_phs_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, ctypes.POINTER(ctypes.c_int32), _dp, _dp]),
+    "frei_phs_apply": (ctypes.c_int, [_vp, _vp, _dp, _dp, _dp, ctypes.c_int, ctypes.c_int, _ip,
+                                      _dp]),
+    "frei_phs_destroy": (ctypes.c_int, [_vp]),
+    "frei_ccf_apply_phs": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int32), _dp, _dp,
+                                          ctypes.c_int, _dp, _dp, _dp, _ip, _dp]),
+    "frei_obs_apply_phs": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _dp, _dp, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_int32), _dp, _dp, _dp,
+                                          ctypes.c_int, _dp, _dp, _ip, _dp]),
+    "frei_brd_apply_phs": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, _dp,
+                                          ctypes.c_int, _ip, _dp]),
 }
 
 _lib = None

@@ -276,6 +276,13 @@ class BatchEngine:
         ``Engine.emergent`` of atmosphere m."""
         return pick(*emergent_call(self, self.n_atm, T, mu, weights, dtaus, want_intensity))
 
+    def phase_curve(self, pc, T, dtaus=None, keep=False):
+        """The atmospheres as the cells of a planet's surface, integrated over the visible disk
+        at every orbital phase of ``pc`` (:class:`~frei_amd.phasecurve.PhaseCurve`, K16) ->
+        [n_phase][n_lam]: ``T`` and ``dtaus`` as :meth:`emergent`.  ``keep=True`` leaves the
+        result on the device (:class:`~frei_amd.phasecurve.PhaseSpectra`)."""
+        return pc.integrate(self, T, dtaus=dtaus, keep=keep)
+
     def post_timing(self):
         """HIP-event milliseconds of the kernels of the last :meth:`post`, :meth:`transit` or
         :meth:`emergent` call."""
@@ -377,6 +384,14 @@ class BatchResult(list):
         (BatchEngine.emergent: angles, weights and the return as there)."""
         T = np.array([np.asarray(value(r.final_T, "K"), dtype=float) for r in self])
         return self.engine.emergent(T, mu=mu, weights=weights, want_intensity=want_intensity)
+
+    def phase_curve(self, pc, keep=False):
+        """The phase spectra [n_phase][n_lam] of ``pc``
+        (:class:`~frei_amd.phasecurve.PhaseCurve`, K16) from each record's ``final_T`` and the
+        dtaus the run left on the device (BatchEngine.phase_curve): atmosphere ``m`` of the run
+        is row ``m`` of ``pc.select``."""
+        T = np.array([np.asarray(value(r.final_T, "K"), dtype=float) for r in self])
+        return self.engine.phase_curve(pc, T, keep=keep)
 
     def observe(self, instrument, kind="eclipse", depth=None, weighting=None, data=None,
                 sigma=None, R_p=None, R_star=None, broadening=None):

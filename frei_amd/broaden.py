@@ -269,7 +269,9 @@ class Broadening(DeviceObject):
         Quantity's numbers as they are, its unit put back).  ``x=None`` with ``engine=`` (an
         Engine or BatchEngine on the whole axis) takes the emergent spectra resident in the
         engine's flux state; an :class:`~frei_amd.modelgrid.InterpolatedSpectra` as ``x`` takes
-        what ``ModelGrid.interpolate(keep=True)`` left on the device.  ``form`` 0 picks the
+        what ``ModelGrid.interpolate(keep=True)`` left on the device, a
+        :class:`~frei_amd.phasecurve.PhaseSpectra` what ``PhaseCurve.integrate(keep=True)`` left
+        there.  ``form`` 0 picks the
         kernel, a member of ``FORMS`` forces it
         (``form_used`` records the choice).  ``keep=True`` leaves the result on the device and
         returns a :class:`BroadenedSpectra` for ``CrossCorrelator.correlate`` or
@@ -277,7 +279,7 @@ class Broadening(DeviceObject):
         kept = kept_suffix(x)
         if kept == "_brd":
             raise TypeError("a BroadenedSpectra cannot be broadened again: pass an array")
-        x, ctx, itp, n_atm, single, unit = resident_or_host(
+        x, ctx, src, n_atm, single, unit = resident_or_host(
             x, engine, self.n_lam, ("a broadener", "a window"))
         out = None if keep else np.empty((n_atm, self.n_lam))
         used, ms = ctypes.c_int(0), ctypes.c_double(0.0)
@@ -285,8 +287,8 @@ class Broadening(DeviceObject):
         self._serial += 1                          # whatever was kept ends with this call
         tail = (n_atm, int(form), N.dptr(out), 1 if keep else 0, ctypes.byref(used),
                 ctypes.byref(ms))
-        if itp is not None:
-            N.check(N.lib().frei_brd_apply_itp(handle, itp, *tail))
+        if src is not None:
+            N.check(getattr(N.lib(), "frei_brd_apply" + kept)(handle, src, *tail))
         else:
             N.check(N.lib().frei_brd_apply(handle, ctx, N.dptr(x), *tail))
         self._record(used, ms)

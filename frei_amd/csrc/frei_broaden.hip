@@ -335,18 +335,19 @@ int frei_brd_norm(frei_brd* b, double* norm) {
   return 0;
 }
 
-// The three sources of x — a host array, a context's emergent rows, an interpolator's kept
-// result (K15) — feed the same x and stride below.
-static int brd_apply_impl(frei_brd* b, frei_ctx* ctx, const double* x, frei_itp* itp, int n_atm,
-                          int form, double* out, int keep, int* form_used, double* kernel_ms) {
+// The four sources of x — a host array, a context's emergent rows, an interpolator's kept
+// result (K15), a phase integrator's (K16) — feed the same x and stride below.
+static int brd_apply_impl(frei_brd* b, frei_ctx* ctx, const double* x, frei_itp* itp,
+                          frei_phs* phs, int n_atm, int form, double* out, int keep,
+                          int* form_used, double* kernel_ms) {
   if (!b) return set_error("frei_brd_apply: null handle");
-  if (!x && !ctx && !itp) return set_error("frei_brd_apply: x and ctx are both null");
+  if (!x && !ctx && !itp && !phs) return set_error("frei_brd_apply: x and ctx are both null");
   if (!out && !keep) return set_error("frei_brd_apply: out is null and keep is not set");
   if (n_atm < 1) return set_error("frei_brd_apply: n_atm must be >= 1");
   if (form < 0 || form > 2)
     return set_error("frei_brd_apply: form must be 0 (automatic), 1 (VALU) or 2 (fp64 MFMA)");
   SpectrumRows src;
-  TRY(spectrum_rows(x, ctx, nullptr, itp, n_atm, b->n_lam, b->device, b->stream, "broadener",
+  TRY(spectrum_rows(x, ctx, nullptr, itp, phs, n_atm, b->n_lam, b->device, b->stream, "broadener",
                     "frei_brd_apply", &src));
   int f = form;
   if (f == 0)
@@ -414,13 +415,22 @@ static int brd_apply_impl(frei_brd* b, frei_ctx* ctx, const double* x, frei_itp*
 
 int frei_brd_apply(frei_brd* b, frei_ctx* ctx, const double* x, int n_atm, int form,
                    double* out, int keep, int* form_used, double* kernel_ms) {
-  return brd_apply_impl(b, ctx, x, nullptr, n_atm, form, out, keep, form_used, kernel_ms);
+  return brd_apply_impl(b, ctx, x, nullptr, nullptr, n_atm, form, out, keep, form_used,
+                        kernel_ms);
 }
 
 int frei_brd_apply_itp(frei_brd* b, frei_itp* src, int n_atm, int form, double* out, int keep,
                        int* form_used, double* kernel_ms) {
   if (!src) return set_error("frei_brd_apply_itp: null interpolator");
-  return brd_apply_impl(b, nullptr, nullptr, src, n_atm, form, out, keep, form_used, kernel_ms);
+  return brd_apply_impl(b, nullptr, nullptr, src, nullptr, n_atm, form, out, keep, form_used,
+                        kernel_ms);
+}
+
+int frei_brd_apply_phs(frei_brd* b, frei_phs* src, int n_atm, int form, double* out, int keep,
+                       int* form_used, double* kernel_ms) {
+  if (!src) return set_error("frei_brd_apply_phs: null phase integrator");
+  return brd_apply_impl(b, nullptr, nullptr, nullptr, src, n_atm, form, out, keep, form_used,
+                        kernel_ms);
 }
 
 }  // extern "C"

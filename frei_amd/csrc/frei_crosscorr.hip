@@ -507,11 +507,11 @@ int frei_ccf_destroy(frei_ccf* c) {
   return 0;
 }
 
-// The four sources of x — a host array, a context's emergent rows, a broadener's kept result
-// (K13), an interpolator's (K15) — feed the same src and stride below.
+// The five sources of x — a host array, a context's emergent rows, a broadener's kept result
+// (K13), an interpolator's (K15), a phase integrator's (K16) — feed the same src and stride below.
 static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd* brd,
-                          frei_itp* itp, int n_atm, const double* den, int n_lib, const int32_t* select,
-                          const double* scale, const double* offset, int form, double* sfg,
+                          frei_itp* itp, frei_phs* phs, int n_atm, const double* den, int n_lib,
+                          const int32_t* select, const double* scale, const double* offset, int form, double* sfg,
                           double* sg, double* sgg, int* form_used, double* kernel_ms) {
   if (!c) return set_error("frei_ccf_apply: null handle");
   if (!sfg && !sg && !sgg && !c->keep)
@@ -519,14 +519,15 @@ static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd*
   // the sums to compute: those asked for; in keep mode with none asked for, all three
   const bool all = !sfg && !sg && !sgg;
   const bool w_fg = sfg || all, w_g = sg || all, w_gg = sgg || all;
-  if (!x && !ctx && !brd && !itp) return set_error("frei_ccf_apply: x and ctx are both null");
+  if (!x && !ctx && !brd && !itp && !phs)
+    return set_error("frei_ccf_apply: x and ctx are both null");
   if (n_atm < 1) return set_error("frei_ccf_apply: n_atm must be >= 1");
   if (form < 0 || form > 2)
     return set_error("frei_ccf_apply: form must be 0 (automatic), 1 (VALU) or 2 (fp64 MFMA)");
   if (den && n_lib < 1) return set_error("frei_ccf_apply: n_lib must be >= 1 with den");
   if (den) TRY(check_select("frei_ccf_apply", select, n_atm, n_lib));
   SpectrumRows rows;
-  TRY(spectrum_rows(x, ctx, brd, itp, n_atm, c->n_lam, c->device, c->stream, "correlator",
+  TRY(spectrum_rows(x, ctx, brd, itp, phs, n_atm, c->n_lam, c->device, c->stream, "correlator",
                     "frei_ccf_apply", &rows));
   int f = form;
   if (f == 0) f = c->n_exp >= kMfmaFromExposures ? 2 : 1;
@@ -634,8 +635,8 @@ int frei_ccf_apply(frei_ccf* c, frei_ctx* ctx, const double* x, int n_atm, const
                    int n_lib, const int32_t* select, const double* scale, const double* offset,
                    int form, double* sfg, double* sg, double* sgg, int* form_used,
                    double* kernel_ms) {
-  return ccf_apply_impl(c, ctx, x, nullptr, nullptr, n_atm, den, n_lib, select, scale, offset, form, sfg,
-                        sg, sgg, form_used, kernel_ms);
+  return ccf_apply_impl(c, ctx, x, nullptr, nullptr, nullptr, n_atm, den, n_lib, select, scale,
+                        offset, form, sfg, sg, sgg, form_used, kernel_ms);
 }
 
 int frei_ccf_keep(frei_ccf* c, int on) {
@@ -650,8 +651,8 @@ int frei_ccf_apply_brd(frei_ccf* c, frei_brd* src, int n_atm, const double* den,
                        int form, double* sfg, double* sg, double* sgg, int* form_used,
                        double* kernel_ms) {
   if (!src) return set_error("frei_ccf_apply_brd: null broadener");
-  return ccf_apply_impl(c, nullptr, nullptr, src, nullptr, n_atm, den, n_lib, select, scale,
-                        offset, form, sfg, sg, sgg, form_used, kernel_ms);
+  return ccf_apply_impl(c, nullptr, nullptr, src, nullptr, nullptr, n_atm, den, n_lib, select,
+                        scale, offset, form, sfg, sg, sgg, form_used, kernel_ms);
 }
 
 int frei_ccf_apply_itp(frei_ccf* c, frei_itp* src, int n_atm, const double* den, int n_lib,
@@ -659,8 +660,17 @@ int frei_ccf_apply_itp(frei_ccf* c, frei_itp* src, int n_atm, const double* den,
                        int form, double* sfg, double* sg, double* sgg, int* form_used,
                        double* kernel_ms) {
   if (!src) return set_error("frei_ccf_apply_itp: null interpolator");
-  return ccf_apply_impl(c, nullptr, nullptr, nullptr, src, n_atm, den, n_lib, select, scale,
-                        offset, form, sfg, sg, sgg, form_used, kernel_ms);
+  return ccf_apply_impl(c, nullptr, nullptr, nullptr, src, nullptr, n_atm, den, n_lib, select,
+                        scale, offset, form, sfg, sg, sgg, form_used, kernel_ms);
+}
+
+int frei_ccf_apply_phs(frei_ccf* c, frei_phs* src, int n_atm, const double* den, int n_lib,
+                       const int32_t* select, const double* scale, const double* offset,
+                       int form, double* sfg, double* sg, double* sgg, int* form_used,
+                       double* kernel_ms) {
+  if (!src) return set_error("frei_ccf_apply_phs: null phase integrator");
+  return ccf_apply_impl(c, nullptr, nullptr, nullptr, nullptr, src, n_atm, den, n_lib, select,
+                        scale, offset, form, sfg, sg, sgg, form_used, kernel_ms);
 }
 
 }  // extern "C"

@@ -539,6 +539,17 @@ struct CtxRows {
   hipStream_t stream;
 };
 int ctx_emergent_rows(frei_ctx* c, CtxRows* out);
+// K16 (frei_phase.hip) runs frei_emergent's recurrence on a context's columns: its Planck
+// constants c1[n_lam], hcl[n_lam] and, with need_dtaus, the dtaus[n_atm][nL][n_lam] the last run
+// kept ("no device dtaus" when there is none; dtaus is null without need_dtaus), all on `device`
+// and ordered behind the work queued on `stream`.
+struct CtxColumns {
+  const double *dtaus, *c1, *hcl;
+  int64_t n_lam;
+  int nL, n_atm, device;
+  hipStream_t stream;
+};
+int ctx_columns(frei_ctx* c, bool need_dtaus, CtxColumns* out);
 }  // namespace frei
 struct frei_brd;
 namespace frei {
@@ -561,6 +572,18 @@ struct ItpRows {
   int n_query, device;
 };
 int itp_kept_rows(frei_itp* p, ItpRows* out);
+}  // namespace frei
+struct frei_phs;
+namespace frei {
+// K16 (frei_phase.hip): what the phase integrator's last apply kept, [n_phase][n_lam] doubles
+// back to back on `device`, complete (its stream was synchronised); rows is null with nothing
+// kept.
+struct PhsRows {
+  const double* rows;
+  int64_t n_lam;
+  int n_phase, device;
+};
+int phs_kept_rows(frei_phs* p, PhsRows* out);
 }  // namespace frei
 struct frei_ccf;
 namespace frei {

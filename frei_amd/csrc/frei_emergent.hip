@@ -49,8 +49,9 @@ constexpr int kAhead = 4;
 static_assert(kTile >= 1 && kTile <= 8 && kAhead >= 1, "tile of 1 .. 8 angles");
 constexpr double kTwoPi = 6.283185307179586;
 
-// exp_em, planck_em and shell_step (one exponential polynomial per shell and angle) are in
-// frei_math.h with the primitives they are built on.
+// exp_em, planck_em, shell_step (one exponential polynomial per shell and angle) and column_walk
+// (the walk of one tile's rays up a column, shared with K16) are in frei_math.h with the
+// primitives they are built on.
 
 // The angles k0 .. k0 + TI - 1 of one column: the walk from level 1 to the top.  col: the
 // column's row 0; it[l] = 1 / T_l for l = 1 .. nS + 1 (the virtual top level repeats the last).
@@ -63,30 +64,9 @@ __device__ __forceinline__ void emergent_pass(const double* __restrict__ col, in
                                               const double* __restrict__ ck, int k0,
                                               double* __restrict__ out, double& F) {
   double w[TI], I[TI];
-  double Bl = planck_em(c1, hcl, it[1]);          // opaque base at level 1
 #pragma unroll
-  for (int t = 0; t < TI; ++t) {
-    w[t] = imu[k0 + t];
-    I[t] = Bl;
-  }
-  // rows past the last shell are clamped to it: loaded, never used
-  double d[kAhead];
-#pragma unroll
-  for (int u = 0; u < kAhead; ++u) d[u] = col[(int64_t)min(1 + u, nS) * n];
-  for (int l0 = 1; l0 <= nS; l0 += kAhead) {
-#pragma unroll
-    for (int u = 0; u < kAhead; ++u) {
-      const int l = l0 + u;
-      if (l <= nS) {
-        const double dt = d[u];
-        d[u] = col[(int64_t)min(l + kAhead, nS) * n];
-        const double Bn = planck_em(c1, hcl, it[l + 1]);
-#pragma unroll
-        for (int t = 0; t < TI; ++t) shell_step(I[t], dt * w[t], Bl, Bn);
-        Bl = Bn;
-      }
-    }
-  }
+  for (int t = 0; t < TI; ++t) w[t] = imu[k0 + t];
+  column_walk<TI, kAhead>(col, n, nS, c1, hcl, it, w, I);
 #pragma unroll
   for (int t = 0; t < TI; ++t) {
     if (out) out[(int64_t)(k0 + t) * n] = I[t];

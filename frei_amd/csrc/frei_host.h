@@ -1,6 +1,6 @@
 // frei_host.h — the host code every translation unit's C entry points share: the error macros,
 // device allocation and copies, the scaffold of one post-processing call (DeviceCall) and the
-// resolution of a spectrum's three sources.  Host code only; a new post-processing call starts
+// resolution of a spectrum's sources.  Host code only; a new post-processing call starts
 // from DeviceCall and spectrum_rows ("Host scaffold").
 #pragma once
 #include <cstdlib>
@@ -160,21 +160,35 @@ class DeviceCall {
 
 // Where a consumer (an instrument, a correlator, a broadener, an interpolator's library) reads
 // its spectra x[n_atm][n_lam]: the caller's host array (rows stays null: the caller uploads x), a
-// context's emergent rows in place, what a broadener kept (K13) or what an interpolator kept
-// (K15: its queries are the atmospheres).  `noun` is the consumer in the messages, `entry` its C
-// entry point.
+// context's emergent rows in place, what a broadener kept (K13), what an interpolator kept
+// (K15: its queries are the atmospheres) or what a phase integrator kept (K16: its phases are).
+// `noun` is the consumer in the messages, `entry` its C entry point.
 struct SpectrumRows {
   const double* rows;
   int64_t stride;
   hipStream_t stream;
 };
 
-inline int spectrum_rows(const double* x, frei_ctx* ctx, frei_brd* brd, frei_itp* itp, int n_atm,
-                         int64_t n_lam, int device, hipStream_t own, const std::string& noun,
-                         const std::string& entry, SpectrumRows* out) {
+inline int spectrum_rows(const double* x, frei_ctx* ctx, frei_brd* brd, frei_itp* itp,
+                         frei_phs* phs, int n_atm, int64_t n_lam, int device, hipStream_t own,
+                         const std::string& noun, const std::string& entry, SpectrumRows* out) {
   *out = SpectrumRows{nullptr, n_lam, own};
   const std::string N = std::to_string(n_atm);
-  if (itp) {
+  if (phs) {
+    const std::string e = entry + "_phs: ";
+    PhsRows pr{};
+    TRY(phs_kept_rows(phs, &pr));
+    if (!pr.rows) return set_error(e + "the phase integrator holds nothing kept (apply with keep)");
+    if (pr.n_lam != n_lam)
+      return set_error(e + "the phase integrator's n_lam = " + std::to_string(pr.n_lam) +
+                       " is not the " + noun + "'s " + std::to_string(n_lam));
+    if (pr.n_phase != n_atm)
+      return set_error(e + "the phase integrator keeps " + std::to_string(pr.n_phase) +
+                       " phases, not n_atm = " + N);
+    if (pr.device != device)
+      return set_error(e + "phase integrator and " + noun + " live on different devices");
+    out->rows = pr.rows;
+  } else if (itp) {
     const std::string e = entry + "_itp: ";
     ItpRows ir{};
     TRY(itp_kept_rows(itp, &ir));

@@ -226,8 +226,8 @@ int frei_itp_set_nodes(frei_itp* p, frei_ctx* ctx, frei_brd* brd, const double* 
   if (!p) return set_error("frei_itp_set_nodes: null handle");
   if (!x && !ctx && !brd) return set_error("frei_itp_set_nodes: x, ctx and brd are all null");
   SpectrumRows src;
-  TRY(spectrum_rows(x, ctx, brd, nullptr, p->n_node, p->n_lam, p->device, nullptr, "interpolator",
-                    "frei_itp_set_nodes", &src));
+  TRY(spectrum_rows(x, ctx, brd, nullptr, nullptr, p->n_node, p->n_lam, p->device, nullptr,
+                    "interpolator", "frei_itp_set_nodes", &src));
   HIP_TRY(hipSetDevice(p->device));
   if (!p->stream) HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
   // the library and whatever was kept end here, whether or not this call succeeds

@@ -268,4 +268,38 @@ __device__ __forceinline__ void shell_step(double& I, double x, double Bl, doubl
   I = I * e + (Bl * u + Bn * v);
 }
 
+// TI rays through one column, from the opaque base at level 1 to the top: the walk K11
+// (frei_emergent.hip) and K16 (frei_phase.hip) share, so that a ray's intensity is the same bits
+// in both.  col: the column's row 0 (rows n apart); it[l] = 1 / T_l for l = 1 .. nS + 1 (the
+// virtual top level repeats the last); w[t] = 1 / mu of ray t; I[t] receives its intensity.  Each
+// dtaus[l] is loaded once, AHEAD shells ahead of its use (rows past the last shell are clamped to
+// it: loaded, never used), and B_{l+1} is formed once per shell for every ray and becomes the next
+// shell's B_l.
+template <int TI, int AHEAD>
+__device__ __forceinline__ void column_walk(const double* __restrict__ col, int64_t n, int nS,
+                                            double c1, double hcl,
+                                            const double* __restrict__ it, const double (&w)[TI],
+                                            double (&I)[TI]) {
+  double Bl = planck_em(c1, hcl, it[1]);
+#pragma unroll
+  for (int t = 0; t < TI; ++t) I[t] = Bl;
+  double d[AHEAD];
+#pragma unroll
+  for (int u = 0; u < AHEAD; ++u) d[u] = col[(int64_t)min(1 + u, nS) * n];
+  for (int l0 = 1; l0 <= nS; l0 += AHEAD) {
+#pragma unroll
+    for (int u = 0; u < AHEAD; ++u) {
+      const int l = l0 + u;
+      if (l <= nS) {
+        const double dt = d[u];
+        d[u] = col[(int64_t)min(l + AHEAD, nS) * n];
+        const double Bn = planck_em(c1, hcl, it[l + 1]);
+#pragma unroll
+        for (int t = 0; t < TI; ++t) shell_step(I[t], dt * w[t], Bl, Bn);
+        Bl = Bn;
+      }
+    }
+  }
+}
+
 }  // namespace frei

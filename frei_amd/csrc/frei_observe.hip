@@ -278,15 +278,16 @@ int frei_obs_destroy(frei_obs* o) {
   return 0;
 }
 
-// The four sources of x — a host array, a context's emergent rows, a broadener's kept result
-// (K13), an interpolator's (K15) — feed the same x and stride below.
+// The five sources of x — a host array, a context's emergent rows, a broadener's kept result
+// (K13), an interpolator's (K15), a phase integrator's (K16) — feed the same x and stride below.
 static int obs_apply_impl(frei_obs* o, frei_ctx* ctx, const double* x, frei_brd* brd,
-                          frei_itp* itp, int n_atm, const double* num, const double* den, int n_lib,
-                          const int32_t* select, const double* scale, const double* data,
-                          const double* sigma, int form, double* obs, double* chi2,
-                          int* form_used, double* kernel_ms) {
+                          frei_itp* itp, frei_phs* phs, int n_atm, const double* num,
+                          const double* den, int n_lib, const int32_t* select,
+                          const double* scale, const double* data, const double* sigma, int form,
+                          double* obs, double* chi2, int* form_used, double* kernel_ms) {
   if (!o || !obs) return set_error("frei_obs_apply: null handle or null obs");
-  if (!x && !ctx && !brd && !itp) return set_error("frei_obs_apply: x and ctx are both null");
+  if (!x && !ctx && !brd && !itp && !phs)
+    return set_error("frei_obs_apply: x and ctx are both null");
   if (n_atm < 1) return set_error("frei_obs_apply: n_atm must be >= 1");
   if (form < 0 || form > 2)
     return set_error("frei_obs_apply: form must be 0 (automatic), 1 (lane per channel) or 2 "
@@ -302,7 +303,7 @@ static int obs_apply_impl(frei_obs* o, frei_ctx* ctx, const double* x, frei_brd*
                          "] must be > 0 (+inf removes the channel)");
   }
   SpectrumRows src;
-  TRY(spectrum_rows(x, ctx, brd, itp, n_atm, o->n_lam, o->device, o->stream, "instrument",
+  TRY(spectrum_rows(x, ctx, brd, itp, phs, n_atm, o->n_lam, o->device, o->stream, "instrument",
                     "frei_obs_apply", &src));
   const double mean_points = (double)o->nnz / (double)o->K;
   int f = form;
@@ -352,8 +353,8 @@ int frei_obs_apply(frei_obs* o, frei_ctx* ctx, const double* x, int n_atm, const
                    const double* den, int n_lib, const int32_t* select, const double* scale,
                    const double* data, const double* sigma, int form, double* obs, double* chi2,
                    int* form_used, double* kernel_ms) {
-  return obs_apply_impl(o, ctx, x, nullptr, nullptr, n_atm, num, den, n_lib, select, scale, data, sigma,
-                        form, obs, chi2, form_used, kernel_ms);
+  return obs_apply_impl(o, ctx, x, nullptr, nullptr, nullptr, n_atm, num, den, n_lib, select, scale,
+                        data, sigma, form, obs, chi2, form_used, kernel_ms);
 }
 
 int frei_obs_apply_brd(frei_obs* o, frei_brd* src, int n_atm, const double* num,
@@ -361,8 +362,8 @@ int frei_obs_apply_brd(frei_obs* o, frei_brd* src, int n_atm, const double* num,
                        const double* data, const double* sigma, int form, double* obs,
                        double* chi2, int* form_used, double* kernel_ms) {
   if (!src) return set_error("frei_obs_apply_brd: null broadener");
-  return obs_apply_impl(o, nullptr, nullptr, src, nullptr, n_atm, num, den, n_lib, select, scale,
-                        data, sigma, form, obs, chi2, form_used, kernel_ms);
+  return obs_apply_impl(o, nullptr, nullptr, src, nullptr, nullptr, n_atm, num, den, n_lib, select,
+                        scale, data, sigma, form, obs, chi2, form_used, kernel_ms);
 }
 
 int frei_obs_apply_itp(frei_obs* o, frei_itp* src, int n_atm, const double* num,
@@ -370,8 +371,17 @@ int frei_obs_apply_itp(frei_obs* o, frei_itp* src, int n_atm, const double* num,
                        const double* data, const double* sigma, int form, double* obs,
                        double* chi2, int* form_used, double* kernel_ms) {
   if (!src) return set_error("frei_obs_apply_itp: null interpolator");
-  return obs_apply_impl(o, nullptr, nullptr, nullptr, src, n_atm, num, den, n_lib, select, scale,
-                        data, sigma, form, obs, chi2, form_used, kernel_ms);
+  return obs_apply_impl(o, nullptr, nullptr, nullptr, src, nullptr, n_atm, num, den, n_lib, select,
+                        scale, data, sigma, form, obs, chi2, form_used, kernel_ms);
+}
+
+int frei_obs_apply_phs(frei_obs* o, frei_phs* src, int n_atm, const double* num,
+                       const double* den, int n_lib, const int32_t* select, const double* scale,
+                       const double* data, const double* sigma, int form, double* obs,
+                       double* chi2, int* form_used, double* kernel_ms) {
+  if (!src) return set_error("frei_obs_apply_phs: null phase integrator");
+  return obs_apply_impl(o, nullptr, nullptr, nullptr, nullptr, src, n_atm, num, den, n_lib, select,
+                        scale, data, sigma, form, obs, chi2, form_used, kernel_ms);
 }
 
 }  // extern "C"

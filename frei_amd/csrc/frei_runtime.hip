@@ -1415,6 +1415,14 @@ int check_comm(frei_ctx* c) {
   return 0;
 }
 
+// The dtaus a post-processing call reads when the caller passes none: the last run's, kept on
+// the device (a batched run's with keep_dtaus).
+int need_device_dtaus(frei_ctx* c, bool batch) {
+  if (c->d_dtaus && (batch ? c->dtaus_batch_valid : c->dtaus_valid)) return 0;
+  return fail(batch ? "no device dtaus: run frei_run_batch_ex with keep_dtaus first, or pass dtaus"
+                    : "no device dtaus: run frei_run first or pass dtaus");
+}
+
 }  // namespace
 
 namespace frei {
@@ -1424,6 +1432,19 @@ int ctx_emergent_rows(frei_ctx* c, CtxRows* out) {
   out->stride = (int64_t)c->nL * c->nlam;
   out->n_atm = c->n_atm;
   out->n_lam = c->nlam;
+  out->device = c->device;
+  out->stream = c->stream;
+  return 0;
+}
+int ctx_columns(frei_ctx* c, bool need_dtaus, CtxColumns* out) {
+  if (!ready(c)) return fail("context not ready");
+  if (need_dtaus) TRY(need_device_dtaus(c, c->batch_api));
+  out->dtaus = need_dtaus ? c->d_dtaus : nullptr;
+  out->c1 = c->d_c1;
+  out->hcl = c->d_hcl;
+  out->n_lam = c->nlam;
+  out->nL = c->nL;
+  out->n_atm = c->n_atm;
   out->device = c->device;
   out->stream = c->stream;
   return 0;
@@ -2498,14 +2519,6 @@ int frei_comm_p2p_open(frei_ctx* c, const void* handles) {
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   return check_comm(c);
-}
-
-// The dtaus a post-processing call reads when the caller passes none: the last run's, kept on
-// the device (a batched run's with keep_dtaus).
-static int need_device_dtaus(frei_ctx* c, bool batch) {
-  if (c->d_dtaus && (batch ? c->dtaus_batch_valid : c->dtaus_valid)) return 0;
-  return fail(batch ? "no device dtaus: run frei_run_batch_ex with keep_dtaus first, or pass dtaus"
-                    : "no device dtaus: run frei_run first or pass dtaus");
 }
 
 // dtaus for a single context's post-processing: the caller's host array or frei_run's.

@@ -213,6 +213,8 @@ class ModelGrid(DeviceObject):
         kept = kept_suffix(spectra)
         if kept == "_itp":
             raise TypeError("an InterpolatedSpectra cannot be a model grid's nodes: pass an array")
+        if kept == "_phs":
+            raise TypeError("a PhaseSpectra cannot be a model grid's nodes: pass an array")
         x, ctx, brd, n_rows, _, _ = resident_or_host(
             spectra, engine, self.n_lam, ("a model grid", "its wavelength axis"))
         if n_rows != self.n_node:

@@ -892,6 +892,90 @@ int frei_obs_apply_itp(frei_obs* o, frei_itp* src, int n_atm, const double* num,
 int frei_brd_apply_itp(frei_brd* b, frei_itp* src, int n_atm, int form, double* out, int keep,
                        int* form_used, double* kernel_ms);
 
+/*
+ * Phase curves (K16): the columns of a context seen as the cells of a planet's surface and
+ * integrated over the visible disk at every orbital phase, formed and kept on the device.  The
+ * reference has no counterpart; this is the definition.
+ * A phase integrator on `device` holds a geometry of n_cell >= 1 cells at n_phase >= 1 phases:
+ *   select[n_cell]       the atmosphere (row of the context) of each cell, >= 0; several cells
+ *                        may name the same row
+ *   mu[n_phase][n_cell]  the cosine of the angle between the cell's normal and the observer at
+ *                        that phase, finite and <= 1
+ *   coef[n_phase][n_cell] the cell's weight in the disk integral, its solid angle times mu, formed
+ *                        by the caller and never recomputed on the device
+ * A pair (p, c) is visible exactly when mu[p][c] > 0.  Pairs with mu <= 0 are skipped: they are
+ * not multiplied by zero and their coef is never read (it may be anything).  For a visible pair
+ * imu = 1.0 / mu is formed here in fp64, as frei_emergent forms it, and must be finite; coef must
+ * be finite and >= 0.  frei_phs_create checks all of it on the host, naming the first offending
+ * index, and touches no device: the plan is uploaded by the first frei_phs_apply and stays
+ * resident on `device` with the handle from then on.
+ */
+typedef struct frei_phs frei_phs;
+int frei_phs_create(frei_phs** out, int device, int n_cell, int n_phase, const int32_t* select,
+                    const double* mu, const double* coef);
+/*
+ * Integrate.  ctx, dtaus and T are those of frei_emergent: dtaus[n_atm][n_layers][n_lam] is a host
+ * array to upload, or NULL for the device copy the last frei_run / frei_run_batch_ex(keep_dtaus)
+ * left; T[n_atm][n_layers] is a host array, always given; a wavelength-slice context gives its
+ * own columns.  Per phase p and wavelength j:
+ *   I_pc      = the intensity frei_emergent defines for atmosphere select[c] at the angle
+ *               mu[p][c], by that function's own operations: bitwise its intensity[select[c]][k][j]
+ *               for mu[k] = mu[p][c]
+ *   out[p][j] = sum over the visible cells c, ascending, of coef[p][c] * I_pc: the first visible
+ *               term starts the sum, every later one enters by one multiply and one add, never
+ *               contracted (frei_emergent's flux order; NumPy's acc + w * x)
+ *   a phase with no visible cell gives exactly 0.0
+ * There is no 2 pi factor: with coef = solid angle x mu a uniform planet gives the flux of
+ * frei_emergent in the same unit (the sum of coef over the visible hemisphere is pi).
+ * out[n_phase][n_lam] receives the result; it may be NULL when keep is set.  The result is formed
+ * in a device buffer the handle owns, reused from call to call and grown when a call needs more.
+ * With keep != 0 it stays valid there until the next frei_phs_apply (kept or not, successful or
+ * not once its arguments are accepted) or frei_phs_destroy; frei_obs_apply_phs,
+ * frei_brd_apply_phs and frei_ccf_apply_phs read it there.
+ * Kernel: one lane per wavelength; a block owns 256 wavelengths and a tile of 8 consecutive phases
+ * whose sums live in registers, and walks the cells in ascending order.  Per tile the list of
+ * cells to visit (those visible at one of its phases or more) and, per visit, the phases that see
+ * the cell are built on the host at create: a cell's column is loaded once per tile, B_{l+1} is
+ * formed once per shell for all the tile's rays through the cell, an invisible pair costs nothing.
+ * There is one form: form 0 (automatic) and form 1 name it, *form_used receives 1.
+ * Guarantees.  No atomics.  Results are bitwise the same from call to call; row p is bitwise the
+ * row of a handle that holds phase p alone; an output does not change when other phases are
+ * added, permuted or dropped, or when cells invisible at p are added; two cells on one row give
+ * the bits of the same data in two rows; a single context gives the bits of a one-atmosphere
+ * batch.  (A pair of cells with the same row and the same mu may be evaluated once and reused —
+ * the north/south symmetry at 90 degrees inclination; the bits would be the same.  It is allowed,
+ * not required, and not done.)  A NaN or inf in a column of atmosphere m at wavelength j reaches
+ * exactly the outputs (p, j) at which some cell with select = m is visible, and no other
+ * wavelength or phase; nothing in the columns is checked.
+ * *form_used and *kernel_ms (HIP events around the kernel only) may be NULL.  Errors (return
+ * codes; handle and context stay usable): a null handle, context or T; out null without keep; a
+ * form outside 0 .. 1; a context on another device; a select entry >= n_atm (the message names the
+ * cell); a T[m][l], l >= 1, not finite and positive in an atmosphere some visible cell uses (the
+ * other atmospheres' temperatures are not read); no device dtaus; n_phase / 8 beyond the launch
+ * grid (65535).
+ */
+int frei_phs_apply(frei_phs* phs, frei_ctx* ctx, const double* dtaus, const double* T,
+                   double* out, int keep, int form, int* form_used, double* kernel_ms);
+int frei_phs_destroy(frei_phs* phs);
+/*
+ * frei_ccf_apply, frei_obs_apply and frei_brd_apply with the result `src` kept (frei_phs_apply
+ * with keep) as their x: a fifth source, read where it lies.  The phases play the role of the
+ * atmospheres (n_atm = n_phase): select, scale, offset and den are per phase.  The other
+ * arguments and the results are those of the plain calls, bitwise what they give for a host copy
+ * of the same numbers.  Errors: a null phase integrator, one with nothing kept, or one of another
+ * n_lam, n_phase or device.
+ */
+int frei_ccf_apply_phs(frei_ccf* c, frei_phs* src, int n_atm, const double* den, int n_lib,
+                       const int32_t* select, const double* scale, const double* offset,
+                       int form, double* sfg, double* sg, double* sgg, int* form_used,
+                       double* kernel_ms);
+int frei_obs_apply_phs(frei_obs* o, frei_phs* src, int n_atm, const double* num,
+                       const double* den, int n_lib, const int32_t* select, const double* scale,
+                       const double* data, const double* sigma, int form, double* obs,
+                       double* chi2, int* form_used, double* kernel_ms);
+int frei_brd_apply_phs(frei_brd* b, frei_phs* src, int n_atm, int form, double* out, int keep,
+                       int* form_used, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
