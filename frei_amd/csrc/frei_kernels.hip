@@ -556,14 +556,57 @@ __host__ __device__ inline int64_t red_lds_doubles(int red_rows, int ns, int nw 
          (red_rows == 2 ? (int64_t)nw * 2 * 4 * kStageRow : 0);
 }
 
+// ---------------------------------------------------------------- step records
+// The head of layer i's step record in direction `dir`, for any of the three record types
+// (StepP, FastStep, FastStepS): twostream.py:356-363 (T_1, T_2, p_2 of the top layer), :227-231
+// (dm).  T and P are anything indexed by layer — arrays, or the trailing update's LayerPair of
+// two temperatures held in registers — and entry i + 1 is read only below the top layer (the
+// arrays end at i there).
+template <class Rec, class TV, class PV>
+__device__ __forceinline__ void step_head(Rec& f, const SetupArgs& u, TV T, PV P, int dir,
+                                          int i) {
+  const int top = (dir == kEmit && i == u.n_layers - 1) ? 1 : 0;
+  f.layer = i;
+  f.top = top;
+  f.iT1 = 1.0 / T[i];
+  f.iT2 = top ? f.iT1 : 1.0 / T[i + 1];
+  const double p2 = top ? u.p_top2 : P[i + 1];
+  f.dm = (P[i] - p2) / u.g;
+}
+// Layers l and l + 1 as a view for step_head: v[l] = at, v[l + 1] = above.
+struct LayerPair {
+  int l;
+  double at, above;
+  __device__ double operator[](int i) const { return i == l ? at : above; }
+};
+// Shared-bracket step record k of direction `dir` (every field but the mixing ratios):
+// step_head, then the T bracket and weights at the layer's temperature (opacity.py:250-263).
+// Used by setup_sweep, by the sweeps that form their own records (stage_records) and by the
+// trailing update.
+template <class TV, class PV>
+__device__ __forceinline__ void step_s_core(const SetupArgs& u, TV T, PV P, const double* tnodes,
+                                            const SpecMeta& sm, const PMeta& pm, int dir, int k,
+                                            FastStepS& f) {
+  const int i = step_layer(dir, k, u.n_layers);
+  step_head(f, u, T, P, dir, i);
+  int64_t off;
+  double wlo, whi;
+  fast_term(sm, pm, tnodes, T[i], off, wlo, whi);
+  f.off = off;
+  f.wlo = wlo;
+  f.whi = whi;
+}
+// A shared-bracket record's mixing ratios: mmr_of(s) for the nS species, zero beyond them.
+template <class M>
+__device__ __forceinline__ void step_s_mmr(FastStepS& f, int nS, M&& mmr_of) {
+  for (int s = 0; s < kMaxFastS; ++s) f.mmr[s] = s < nS ? mmr_of(s) : 0.0;
+}
+
 // The sweep's step records formed in its own prologue (FastArgs.rec_on: contracted table,
 // shared brackets, fixed mmr) from the temperatures the previous update kernel left: T, p and
 // the sorted T nodes are staged in `scratch` (LDS), then thread k forms record k into `dst`
 // (LDS) with setup_sweep's expressions — the records the update kernel would have written, bit
 // for bit, without that kernel's record step on the critical path.  Ends with a block barrier.
-__device__ __forceinline__ void step_s_core(const SetupArgs& u, const double* T, const double* P,
-                                            const double* tnodes, const SpecMeta& sm,
-                                            const PMeta& pm, int dir, int k, FastStepS& f);
 __device__ inline void atm_view(SetupArgs& u, int m);
 __host__ __device__ inline int64_t rec_scratch_doubles(const FastArgs& a) {
   return a.rec_on ? 2 * (int64_t)a.rec.n_layers + a.rec.n_tnodes : 0;
@@ -2245,29 +2288,6 @@ void launch_log_ratio(const double* p, double p_top2, int nL, double* lnp, hipSt
 }
 
 // ---------------------------------------------------------------- setup (T -> terms)
-// Shared-bracket step record k of direction `dir` from temperatures T and pressures P (every
-// field but the mixing ratios): twostream.py:356-363 (T_1, T_2, p_2 of the top layer), :227-231
-// (dm), opacity.py:250-263 (the T bracket and weights).  Used by setup_sweep and by the sweeps
-// that form their own records (stage_records).
-__device__ __forceinline__ void step_s_core(const SetupArgs& u, const double* T, const double* P,
-                                            const double* tnodes, const SpecMeta& sm,
-                                            const PMeta& pm, int dir, int k, FastStepS& f) {
-  const int nL = u.n_layers;
-  const int i = step_layer(dir, k, nL);
-  const int top = (dir == kEmit && i == nL - 1) ? 1 : 0;
-  f.layer = i;
-  f.top = top;
-  f.iT1 = 1.0 / T[i];
-  f.iT2 = top ? f.iT1 : 1.0 / T[i + 1];
-  const double p2 = top ? u.p_top2 : P[i + 1];
-  f.dm = (P[i] - p2) / u.g;
-  int64_t off;
-  double wlo, whi;
-  fast_term(sm, pm, tnodes, T[i], off, wlo, whi);
-  f.off = off;
-  f.wlo = wlo;
-  f.whi = whi;
-}
 // Step records [kb, ke) of the sweep in direction `dir` from temperatures T (only the layers
 // of those steps and the ones above them are read), written by the threads tid = 0, 1, ...
 // of the caller's group (nthr of them).  pmeta / mmr of species s at layer i are read at
@@ -2291,22 +2311,13 @@ __device__ void setup_sweep(const SetupArgs& u, const double* T, const double* P
       const int i = step_layer(dir, k, nL);
       FastStepS* f = u.ssteps + k;
       step_s_core(u, T, P, tnodes, spec[0], pmeta[MI(0, i)], dir, k, *f);
-      for (int s = 0; s < kMaxFastS; ++s) f->mmr[s] = s < nS ? MMR(s, i) : 0.0;
+      step_s_mmr(*f, nS, [&](int s) { return MMR(s, i); });
     }
     return;
   }
   if (u.fast) {
-    for (int k = kb + tid; k < ke; k += nthr) {
-      const int i = step_layer(dir, k, nL);
-      FastStep* f = u.fsteps + k;
-      const int top = (dir == kEmit && i == nL - 1) ? 1 : 0;
-      f->layer = i;
-      f->top = top;
-      f->iT1 = 1.0 / T[i];
-      f->iT2 = top ? f->iT1 : 1.0 / T[i + 1];
-      const double p2 = top ? u.p_top2 : P[i + 1];
-      f->dm = (P[i] - p2) / u.g;
-    }
+    for (int k = kb + tid; k < ke; k += nthr)
+      step_head(u.fsteps[k], u, T, P, dir, step_layer(dir, k, nL));
     for (int idx = tid; idx < (ke - kb) * kMaxFastS; idx += nthr) {
       const int k = kb + idx / kMaxFastS, s = idx % kMaxFastS;
       FastStep* f = u.fsteps + k;
@@ -2335,14 +2346,8 @@ __device__ void setup_sweep(const SetupArgs& u, const double* T, const double* P
     return;
   }
   for (int k = kb + tid; k < ke; k += nthr) {   // generic kernel's step records
-    const int i = step_layer(dir, k, nL);
     StepP sp;
-    sp.layer = i;
-    sp.top = (dir == kEmit && i == nL - 1) ? 1 : 0;
-    sp.iT1 = 1.0 / T[i];
-    sp.iT2 = sp.top ? sp.iT1 : 1.0 / T[i + 1];                         // twostream.py:358-363
-    const double p2 = sp.top ? u.p_top2 : P[i + 1];
-    sp.dm = (P[i] - p2) / u.g;
+    step_head(sp, u, T, P, dir, step_layer(dir, k, nL));
     sp.pad = 0;
     u.steps[k] = sp;
   }
@@ -2434,6 +2439,91 @@ __device__ __forceinline__ double layer_dT_post(const double* Fb, const LayerPre
 __device__ double layer_dT(const double* Fb, double T1, double T2, double p1, double p2,
                            double lnp, double g, double m_bar, double alpha) {
   return layer_dT_post(Fb, layer_pre(T1, T2, p1, p2, lnp, g, m_bar, alpha));
+}
+
+// The three updates (update_kernel: separate; update_fused_body: fused and chained;
+// tail_update_slot: trailing) differ in where a layer's inputs come from and in how its new T
+// and its convergence bit leave; what they decide per layer is written once, in
+//   layer_bookkeep   core.py:303-311 (history pair, sign flips) and the convergence test
+//   rank_order_sum   the P2P exchange's sum over ranks (fused and trailing)
+//   row_step, wave_sums, block_sum   reduce_kernel's tree over the eight rows of a layer
+//   step_head, step_s_core, step_s_mmr (with the sweeps' step records, above)
+//                    twostream.py:356-363, 227-231, opacity.py:250-263
+
+// Layer l's T-P history state before the update (absorb with tracking; unused otherwise).
+struct LayerHist {
+  double Tb, Ta;        // T entering this iteration's absorb sweep, T after the previous absorb
+  int flips, prev, nd;  // sign flips so far, the last difference's sign, differences seen
+};
+
+// Layer l's bookkeeping for T-P iteration `it`, given its dT and new temperature: the optional
+// dT output; emit: T entering the absorb sweep; absorb: the history column pair, the sign-flip
+// count and the layer's state.  Returns whether the layer counts as converged (true where the
+// convergence test does not apply: no tracking, or an emit sweep).
+__device__ __forceinline__ bool layer_bookkeep(const UpdateArgs& a, int l, int it, double dT,
+                                               double Tnew, LayerHist h) {
+  const int nL = a.su.n_layers;
+  if (a.dT_out) a.dT_out[l] = dT;
+  if (!a.track) return true;
+  if (a.dir == kEmit) {
+    a.Tb[l] = Tnew;  // temperature entering the absorb sweep
+    return true;
+  }
+  // absorb history column pair [T_before, T_after] (core.py:303-307)
+  if (it < a.hist_cap) {
+    a.hist[((int64_t)it * 2 + 0) * nL + l] = h.Tb;
+    a.hist[((int64_t)it * 2 + 1) * nL + l] = Tnew;
+  }
+  // incremental sign-flip count over the concatenated history (core.py:308-311)
+  const double d0 = h.Tb - h.Ta, d1 = Tnew - h.Tb;
+  for (int q = (it > 0 ? 0 : 1); q < 2; ++q) {
+    const double d = q == 0 ? d0 : d1;
+    const int sgn = (d > 0) - (d < 0);
+    if (h.nd > 0 && sgn != h.prev) ++h.flips;
+    h.prev = sgn;
+    ++h.nd;
+  }
+  a.flips[l] = h.flips;
+  a.prev_sign[l] = h.prev;
+  a.ndiff[l] = h.nd;
+  a.Ta[l] = Tnew;
+  return (h.flips > a.n_zero_crossings) || (fabs(dT) < a.convergence_dT);
+}
+
+// Every rank's sum idx of this sweep added in rank order, this rank's (`own`) from the
+// register: waits for the peers' values (from t0), acquires, then reads them.
+__device__ __forceinline__ double rank_order_sum(const UpdateArgs& a, double own, int64_t idx,
+                                                 long long t0) {
+  for (int r = 0; r < a.p2p.nranks; ++r)
+    if (r != a.push.rank) p2p_wait(a.p2p, r, idx, t0);
+  p2p_acquire();
+  double v = own;
+  for (int r = 0; r < a.p2p.nranks; ++r) {
+    const double x = (r == a.push.rank) ? own : p2p_value(a.p2p, r, idx);
+    v = (r == 0) ? x : v + x;
+  }
+  return v;
+}
+
+// The sweep step whose partial sums are row j of a layer's eight: rows 0..3 step k0 (layer l),
+// rows 4..7 step k1 (layer l + 1); a step that does not exist (-1) reads the other's rows.
+__device__ __forceinline__ int row_step(int j, int k0, int k1) {
+  return (j < 4) ? (k0 >= 0 ? k0 : k1) : (k1 >= 0 ? k1 : k0);
+}
+// reduce_kernel's tree over a 256-thread group's eight per-thread sums: the xor butterfly in
+// each wave, lane 0 stores the wave's sums (wave_sums); after the caller's barrier, row q's
+// waves are added in order (block_sum).
+__device__ __forceinline__ void wave_sums(double (&acc)[8], int tid,
+                                          double (&wsum)[kRedWaves][8]) {
+  for (int j = 0; j < 8; ++j)
+    acc[j] = butterfly_sum(acc[j], tid & 63);   // = the xor-32 ... 1 shfl butterfly
+  if ((tid & 63) == 0)
+    for (int j = 0; j < 8; ++j) wsum[tid >> 6][j] = acc[j];
+}
+__device__ __forceinline__ double block_sum(const double (&wsum)[kRedWaves][8], int q) {
+  double t = wsum[0][q];
+  for (int w = 1; w < kRedWaves; ++w) t += wsum[w][q];
+  return t;
 }
 
 // One workgroup.  Phase 0 issues every global read the kernel needs at once (T, p, sorted
@@ -2528,35 +2618,9 @@ __global__ __launch_bounds__(256) void update_kernel(UpdateArgs a) {
   for (int l = threadIdx.x; l < nL; l += blockDim.x) {
     const double dT = sdT[l];
     const double Tnew = sT[l] - dT;
-    if (a.dT_out) a.dT_out[l] = dT;
-    if (a.track) {
-      if (dir == kEmit) {
-        a.Tb[l] = Tnew;  // temperature entering the absorb sweep
-      } else {
-        const double Tb = sTb[l];
-        // absorb history column pair [T_before, T_after] (core.py:303-307)
-        if (it < a.hist_cap) {
-          a.hist[((int64_t)it * 2 + 0) * nL + l] = Tb;
-          a.hist[((int64_t)it * 2 + 1) * nL + l] = Tnew;
-        }
-        // incremental sign-flip count over the concatenated history (core.py:308-311)
-        int flips = sFl[l], prev = sPv[l], nd = sNd[l];
-        const double d0 = Tb - sTa[l], d1 = Tnew - Tb;
-        for (int q = (it > 0 ? 0 : 1); q < 2; ++q) {
-          const double d = q == 0 ? d0 : d1;
-          const int sgn = (d > 0) - (d < 0);
-          if (nd > 0 && sgn != prev) ++flips;
-          prev = sgn;
-          ++nd;
-        }
-        a.flips[l] = flips;
-        a.prev_sign[l] = prev;
-        a.ndiff[l] = nd;
-        a.Ta[l] = Tnew;
-        const bool c = (flips > a.n_zero_crossings) || (fabs(dT) < a.convergence_dT);
-        if (!c) atomicAnd(&all_conv, 0);
-      }
-    }
+    // (the history staged in LDS: read, not used, where nothing is tracked)
+    if (!layer_bookkeep(a, l, it, dT, Tnew, {sTb[l], sTa[l], sFl[l], sPv[l], sNd[l]}))
+      atomicAnd(&all_conv, 0);
     a.su.T[l] = Tnew;
     sT[l] = Tnew;
   }
@@ -2664,8 +2728,7 @@ __device__ void update_fused_body(const UpdateArgs& a, int lr, int nU, int tid, 
   const double p1 = a.su.p[li];
   const double rp2 = a.su.p[li1];
   const double lnp = a.lnp[li];
-  const double Tb = a.Tb[l], Ta = a.Ta[l];
-  int flips = a.flips[l], prev = a.prev_sign[l], nd = a.ndiff[l];
+  const LayerHist hist{a.Tb[l], a.Ta[l], a.flips[l], a.prev_sign[l], a.ndiff[l]};
   const int sm = min(max(tid - 64, 0), S - 1);
   const PMeta rPm = a.su.pmeta[(int64_t)sm * nL + l];
   const SpecMeta rSp = a.su.spec[sm];
@@ -2681,10 +2744,8 @@ __device__ void update_fused_body(const UpdateArgs& a, int lr, int nU, int tid, 
   // path; a converged run's update only discards them)
   if (k0 >= 0 || k1 >= 0) {
     const double* pj[8];
-    for (int j = 0; j < 8; ++j) {
-      const int k = (j < 4) ? (k0 >= 0 ? k0 : k1) : (k1 >= 0 ? k1 : k0);
-      pj[j] = a.part + part_at(k * 4 + (j & 3), 0, a.nblocks, 4 * (nL - 1));
-    }
+    for (int j = 0; j < 8; ++j)
+      pj[j] = a.part + part_at(row_step(j, k0, k1) * 4 + (j & 3), 0, a.nblocks, 4 * (nL - 1));
     // element of block b in row j: pj[j][b * bs]
     const int64_t bs = part_at(0, 1, a.nblocks, 4 * (nL - 1));
     double acc[8];
@@ -2715,10 +2776,7 @@ __device__ void update_fused_body(const UpdateArgs& a, int lr, int nU, int tid, 
 #pragma unroll
           for (int j = 0; j < 8; ++j) acc[j] += v[u][j];
     }
-    for (int j = 0; j < 8; ++j)
-      acc[j] = butterfly_sum(acc[j], tid & 63);   // = the xor-32 ... 1 shfl butterfly
-    if ((tid & 63) == 0)
-      for (int j = 0; j < 8; ++j) wsum[tid >> 6][j] = acc[j];
+    wave_sums(acc, tid, wsum);
   }
   if (!a.force && conv) {    // converged: carry T into the output buffer (no barrier passed)
     if (tid == 0 && on) publish_T(a, l, Tl, conv, true);
@@ -2739,11 +2797,7 @@ __device__ void update_fused_body(const UpdateArgs& a, int lr, int nU, int tid, 
   }
   __syncthreads();
   TRACE_MARK(1);
-  if (tid < 8) {
-    double t = wsum[0][tid];
-    for (int w = 1; w < kRedWaves; ++w) t += wsum[w][tid];
-    tot[tid] = t;
-  }
+  if (tid < 8) tot[tid] = block_sum(wsum, tid);
   __syncthreads();
   const long long t0 = wall_clock64();
   if (a.p2p.mbox && tid == 64 && k0 >= 0 && on)
@@ -2754,17 +2808,7 @@ __device__ void update_fused_body(const UpdateArgs& a, int lr, int nU, int tid, 
     const int k = tid < 4 ? k0 : k1;
     if (tid < 8 && k >= 0) {
       v = tot[tid];
-      if (a.p2p.mbox) {
-        const double own = v;
-        const int64_t idx = (int64_t)k * 4 + (tid & 3);
-        for (int r = 0; r < a.p2p.nranks; ++r)
-          if (r != a.push.rank) p2p_wait(a.p2p, r, idx, t0);
-        p2p_acquire();
-        for (int r = 0; r < a.p2p.nranks; ++r) {
-          const double x = (r == a.push.rank) ? own : p2p_value(a.p2p, r, idx);
-          v = (r == 0) ? x : v + x;
-        }
-      }
+      if (a.p2p.mbox) v = rank_order_sum(a, v, (int64_t)k * 4 + (tid & 3), t0);
     }
     const int base = (tid & 1) * 4;
     double F[4];
@@ -2778,34 +2822,8 @@ __device__ void update_fused_body(const UpdateArgs& a, int lr, int nU, int tid, 
       sTn[li] = T1 - d;
     }
     if (tid == 0 && on) {
-      // layer l's bookkeeping (update_kernel's expressions)
-      const double dT = d;
-      const double Tnew = Tl - dT;
-      if (a.dT_out) a.dT_out[l] = dT;
-      bool c = true;
-      if (a.track) {
-        if (dir == kEmit) {
-          a.Tb[l] = Tnew;
-        } else {
-          if (it < a.hist_cap) {
-            a.hist[((int64_t)it * 2 + 0) * nL + l] = Tb;
-            a.hist[((int64_t)it * 2 + 1) * nL + l] = Tnew;
-          }
-          const double d0 = Tb - Ta, d1 = Tnew - Tb;
-          for (int q = (it > 0 ? 0 : 1); q < 2; ++q) {
-            const double dd = q == 0 ? d0 : d1;
-            const int sgn = (dd > 0) - (dd < 0);
-            if (nd > 0 && sgn != prev) ++flips;
-            prev = sgn;
-            ++nd;
-          }
-          a.flips[l] = flips;
-          a.prev_sign[l] = prev;
-          a.ndiff[l] = nd;
-          a.Ta[l] = Tnew;
-          c = (flips > a.n_zero_crossings) || (fabs(dT) < a.convergence_dT);
-        }
-      }
+      const double Tnew = Tl - d;
+      const bool c = layer_bookkeep(a, l, it, d, Tnew, hist);
       publish_T(a, l, Tnew, conv, c);
       if (kd < 0) sTn[l] = Tnew;
       update_arrive(a, nU, it, !c);
@@ -2990,10 +3008,8 @@ __device__ __forceinline__ void tail_update_slot(const UpdateArgs& a, int lr, in
   // 256, ... never exists here)
   if (sums) {
     const double* pj[8];
-    for (int j = 0; j < 8; ++j) {
-      const int k = (j < 4) ? (k0 >= 0 ? k0 : k1) : (k1 >= 0 ? k1 : k0);
-      pj[j] = a.part + (int64_t)(k * 4 + (j & 3)) * nb;
-    }
+    for (int j = 0; j < 8; ++j)
+      pj[j] = a.part + (int64_t)(row_step(j, k0, k1) * 4 + (j & 3)) * nb;
     const int b = min(tid, nb - 1);
     unsigned long long x[8];
     auto load_all = [&]() {
@@ -3031,9 +3047,7 @@ __device__ __forceinline__ void tail_update_slot(const UpdateArgs& a, int lr, in
 #endif
     double acc[8];
     for (int j = 0; j < 8; ++j) acc[j] = tid < nb ? 0.0 + __builtin_bit_cast(double, x[j]) : 0.0;
-    for (int j = 0; j < 8; ++j) acc[j] = butterfly_sum(acc[j], tid & 63);
-    if ((tid & 63) == 0)
-      for (int j = 0; j < 8; ++j) wsum[tid >> 6][j] = acc[j];
+    wave_sums(acc, tid, wsum);
   }
   __syncthreads();
   TRACE_MARK(2);
@@ -3051,18 +3065,13 @@ __device__ __forceinline__ void tail_update_slot(const UpdateArgs& a, int lr, in
     if (tid == 0 && on) publish_T(a, l, in.T[l], conv, true);
     return;
   }
-  // this rank's sums in wave order (lanes 0..7: k0's four, then k1's)
-  auto own = [&](int q) {
-    double t = wsum[0][q];
-    for (int w = 1; w < kRedWaves; ++w) t += wsum[w][q];
-    return t;
-  };
+  // this rank's sums in wave order, block_sum (lanes 0..7: k0's four, then k1's)
   // (the push's system-scope release writes back this XCD's L2 while the sweep may still run:
   // cheap because the trailing-update sweep stores its fluxes write-through — with plain flux
   // stores the releases cost 230 against 83 us per T-P iteration, profiles/r06/tail/)
   if (a.p2p.mbox && tid == 64 && k0 >= 0 && on) {   // push while wave 0 waits for the peers
     double t4[4];
-    for (int q = 0; q < 4; ++q) t4[q] = own(q);
+    for (int q = 0; q < 4; ++q) t4[q] = block_sum(wsum, q);
     p2p_push_values(a.push, (int64_t)k0 * 4, t4, 4);
   }
   if (tid >= 64) return;
@@ -3071,19 +3080,8 @@ __device__ __forceinline__ void tail_update_slot(const UpdateArgs& a, int lr, in
   double v = 0.0;
   const int k = tid < 4 ? k0 : k1;
   if (tid < 8 && k >= 0) {
-    v = own(tid);
-    if (a.p2p.mbox) {   // all ranks' sums in rank order (own rank from registers)
-      const double mine = v;
-      const int64_t idx = (int64_t)k * 4 + (tid & 3);
-      const long long t0 = wall_clock64();
-      for (int r = 0; r < a.p2p.nranks; ++r)
-        if (r != a.push.rank) p2p_wait(a.p2p, r, idx, t0);
-      p2p_acquire();
-      for (int r = 0; r < a.p2p.nranks; ++r) {
-        const double xr = (r == a.push.rank) ? mine : p2p_value(a.p2p, r, idx);
-        v = (r == 0) ? xr : v + xr;
-      }
-    }
+    v = block_sum(wsum, tid);
+    if (a.p2p.mbox) v = rank_order_sum(a, v, (int64_t)k * 4 + (tid & 3), wall_clock64());
   }
   const int base = (tid & 1) * 4;
   double F[4];
@@ -3099,55 +3097,17 @@ __device__ __forceinline__ void tail_update_slot(const UpdateArgs& a, int lr, in
   // while lane 0 does the bookkeeping and the convergence arrival (round trips in parallel)
   const int kn = a.next_dir >= 0 ? layer_step(a.next_dir, l, nL) : -1;
   if (tid == 1 && on && kn >= 0) {
-    const int tp = (a.next_dir == kEmit && l == nL - 1) ? 1 : 0;
     FastStepS f{};
-    f.layer = l;
-    f.top = tp;
-    f.iT1 = 1.0 / Tl0;
-    f.iT2 = tp ? f.iT1 : 1.0 / Tn;
-    const double p2 = tp ? a.su.p_top2 : in.p[l + 1];
-    f.dm = (in.p[l] - p2) / a.su.g;
-    int64_t off;
-    double wlo, whi;
-    fast_term(a.su.spec[0], in.pm[l], in.nodes, Tl0, off, wlo, whi);
-    f.off = off;
-    f.wlo = wlo;
-    f.whi = whi;
-    for (int q = 0; q < kMaxFastS; ++q) f.mmr[q] = q < 1 ? in.mmr[l] : 0.0;
+    step_s_core(a.su, LayerPair{l, Tl0, Tn}, in.p, in.nodes, a.su.spec[0], in.pm[l], a.next_dir,
+                kn, f);
+    step_s_mmr(f, 1, [&](int) { return in.mmr[l]; });
     a.su.ssteps[kn] = f;
   }
   if (tid != 0 || !on) return;
-  // layer l's bookkeeping (update_kernel's expressions)
-  const double dT = d;
-  const double Tnew = Tn;
-  if (a.dT_out) a.dT_out[l] = dT;
-  bool c = true;
-  if (a.track) {
-    if (dir == kEmit) {
-      a.Tb[l] = Tnew;
-    } else {
-      const double Tb = in.Tb[l], Ta = in.Ta[l];
-      int flips = in.flips[l], prev = in.prev[l], nd = in.nd[l];
-      if (it < a.hist_cap) {
-        a.hist[((int64_t)it * 2 + 0) * nL + l] = Tb;
-        a.hist[((int64_t)it * 2 + 1) * nL + l] = Tnew;
-      }
-      const double d0 = Tb - Ta, d1 = Tnew - Tb;
-      for (int q = (it > 0 ? 0 : 1); q < 2; ++q) {
-        const double dd = q == 0 ? d0 : d1;
-        const int sgn = (dd > 0) - (dd < 0);
-        if (nd > 0 && sgn != prev) ++flips;
-        prev = sgn;
-        ++nd;
-      }
-      a.flips[l] = flips;
-      a.prev_sign[l] = prev;
-      a.ndiff[l] = nd;
-      a.Ta[l] = Tnew;
-      c = (flips > a.n_zero_crossings) || (fabs(dT) < a.convergence_dT);
-    }
-  }
-  publish_T(a, l, Tnew, conv, c);
+  // (the history from the block's stage: read, not used, where nothing is tracked)
+  const bool c = layer_bookkeep(a, l, it, d, Tn,
+                                {in.Tb[l], in.Ta[l], in.flips[l], in.prev[l], in.nd[l]});
+  publish_T(a, l, Tn, conv, c);
   update_arrive(a, nL, it, !c);
   TRACE_PUT(31);
 }

@@ -70,9 +70,10 @@ Arithmetic-only mutations of a scratch copy of the kernels, loaded through FREI_
   - the weight of a 256-wavelength block's last wavelength multiplied by 0 (every sweep kernel
     but the two-wavelength one): 23 tests fail — the default form from 257 wavelengths up, every
     form but lam2, the slices;
-  - ``flips >= n_zero_crossings`` for ``>``, one implementation at a time: update_kernel fails
-    the fused0 cases and the batched one; update_fused_body the default, chain0, chain2_one_lane
-    and pipe4_tail0 cases; tail_update_slot the pipe4_tail1 cases;
+  - ``flips >= n_zero_crossings`` for ``>`` at its single site (layer_bookkeep, called by
+    update_kernel, update_fused_body and tail_update_slot): all 12 cases of
+    test_convergence_bookkeeping_matches_replay (the six CONV_FORMS, flips and dT, each at its
+    first run: n_iter 1 instead of 40 with n_zero_crossings 0) and the batched test fail;
   - the mixing length formed with the default m_bar instead of the planet's: the steep and the
     mixed family fail with both update kernels;
   - rho0 / cp0 formed with the planet's m_bar: nothing fails, as the algebra above says.
