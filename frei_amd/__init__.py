@@ -14,6 +14,7 @@ from .core import (B_star, F_TOA, Grid, Planet, Spectrum, contribution_function,
 from .crosscorr import CrossCorrelation, CrossCorrelator, kp_vsys_map
 from .broaden import BroadenedSpectra, Broadening, BroadeningKernel
 from .emergent import gauss_angles
+from .lines import LineList
 from .stack import OrbitStack
 from .modelgrid import InterpolatedSpectra, ModelGrid
 from .phasecurve import PhaseCurve, PhaseSpectra, lonlat_cells
@@ -38,4 +39,4 @@ __all__ = ["Planet", "Grid", "Spectrum", "effective_temperature", "wavelength_gr
            "StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum",
            "level_radii", "Instrument", "gauss_angles", "CrossCorrelator", "CrossCorrelation",
            "kp_vsys_map", "OrbitStack", "ModelGrid", "InterpolatedSpectra", "PhaseCurve",
-           "PhaseSpectra", "lonlat_cells"]
+           "PhaseSpectra", "lonlat_cells", "LineList"]

@@ -99,6 +99,11 @@ SIGNATURES = {
                                                   ctypes.c_int, ctypes.c_int, _i64, _dp, _dp,
                                                   _dp, ctypes.c_uint64]),
     "frei_xsec_destroy": (ctypes.c_int, [_vp]),
+    "frei_xsec_create_lines": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _i64, _dp, _dp,
+                                              _dp, _dp, _dp, ctypes.c_double, ctypes.c_double,
+                                              ctypes.c_double, _dp, ctypes.c_int, ctypes.c_int,
+                                              _i64, _dp, _dp, _dp, _dp]),
+    "frei_xsec_values": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _i64, _i64, _fp]),
     "frei_xsec_bin": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, _i64, _dp, ctypes.c_int, _dp,
                                      ctypes.c_int, _dp]),
     "frei_xsec_timing": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _ip]),

@@ -36,6 +36,7 @@ class CrossSection:
         self.wavelength = np.ascontiguousarray(value(wavelength, "um"), dtype=np.float64)
         self.isotopologue = isotopologue
         self._synthetic = None
+        self._lines = None
         if self.opacity.shape != (self.temperature.size, self.pressure.size,
                                   self.wavelength.size):
             raise ValueError("opacity must be (temperature, pressure, wavelength)")
@@ -51,7 +52,17 @@ class CrossSection:
         obj.opacity = None
         obj.isotopologue = isotopologue
         obj._synthetic = int(seed)
+        obj._lines = None
         obj._handles = {}
+        return obj
+
+    @classmethod
+    def _from_lines(cls, make, temperature, pressure, wavelength, isotopologue=None):
+        """Computed on the device from a line list (``LineList.cross_section``): ``make(device)``
+        returns the frei_xsec*; no host copy of the values."""
+        obj = cls.synthetic(temperature, pressure, wavelength, isotopologue=isotopologue)
+        obj._synthetic = None
+        obj._lines = make
         return obj
 
     def handle(self, device=0):
@@ -61,7 +72,9 @@ class CrossSection:
             lib = N.lib()
             h = ctypes.c_void_p()
             nT, npr, nhi = self.temperature.size, self.pressure.size, self.wavelength.size
-            if self._synthetic is not None:
+            if self._lines is not None:
+                h = self._lines(device)
+            elif self._synthetic is not None:
                 N.check(lib.frei_xsec_create_synthetic(
                     ctypes.byref(h), device, nT, npr, nhi, N.dptr(self.temperature),
                     N.dptr(self.pressure), N.dptr(self.wavelength), self._synthetic))
@@ -97,6 +110,25 @@ class CrossSection:
                                       N.dptr(wl_bins), N.dptr(lam), lam.size, N.dptr(T), T.size,
                                       N.dptr(p), p.size, N.dptr(res)))
         return res
+
+    def values(self, t=None, p=None, device=0):
+        """The resident float32 values read back from ``device`` (frei_xsec_values): the whole
+        (temperature, pressure, wavelength) table, the (pressure, wavelength) rows of
+        temperature node ``t``, the (temperature, wavelength) rows of pressure node ``p``, or
+        the one row of node (t, p)."""
+        h = self.handle(device)
+        ts = range(self.temperature.size) if t is None else [int(t)]
+        ps = range(self.pressure.size) if p is None else [int(p)]
+        out = np.empty((len(ts), len(ps), self.wavelength.size), dtype=np.float32)
+        for a, kt in enumerate(ts):
+            for b, kp in enumerate(ps):
+                N.check(N.lib().frei_xsec_values(h, kt, kp, 0, self.wavelength.size,
+                                                 N.fptr(out[a, b])))
+        if t is not None:
+            out = out[0]
+        if p is not None:
+            out = out[..., 0, :]
+        return out
 
     def timing(self, on, device=0):
         ms, n = ctypes.c_double(0), ctypes.c_int(0)

@@ -30,27 +30,7 @@
 
 using namespace frei;
 
-struct frei_xsec {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int nT = 0, np = 0;
-  int64_t nhi = 0;
-  std::vector<double> T, p, wl;  // K, bar, µm (ascending)
-  float* d_x = nullptr;          // [nT][np][nhi]
-  double* d_hdx = nullptr;       // 0.5 * (wl[i+1] - wl[i]), exact mode (lazy)
-  double* d_scratch = nullptr;   // output of frei_xsec_bin(out = NULL)
-  size_t scratch_n = 0;
-  bool timing = false;
-  double t_ms = 0;
-  int t_n = 0;
-  // the per-call plan arrays, kept between calls (slot k: device buffer and its capacity in
-  // bytes): no hipMalloc / hipFree per binning call
-  std::vector<std::pair<void*, size_t>> plan;
-  // pinned host staging of the plan uploads (DMA copies; pageable hipMemcpyAsync stalled the
-  // next kernel launch by milliseconds)
-  char* pinned = nullptr;
-  size_t pinned_cap = 0, pinned_used = 0;
-};
+// struct frei_xsec: frei_host.h (K17, frei_lines.hip, fills one too)
 
 namespace {
 

@@ -455,6 +455,48 @@ int frei_xsec_create_synthetic(frei_xsec** out, int device, int n_T, int n_p, in
                                const double* wl_hi, uint64_t seed);
 int frei_xsec_destroy(frei_xsec* x);
 /*
+ * K17: the cross-section computed line by line from a line list on the device (no reference
+ * counterpart: the reference downloads this table, opacity.py:345-372, 493-540).
+ *
+ * Inputs: n_line lines of nondecreasing position, each with nu0 (cm^-1), S_ref (cm molecule^-1 at
+ * T_ref), E_low (cm^-1), gamma_ref (Lorentz HWHM, cm^-1 per bar at T_ref) and n_exp (its
+ * temperature exponent); mass_amu, T_ref (K), cutoff (cm^-1); q_ratio[n_T] = Q(T_ref) / Q(T_t);
+ * nodes T_nodes[n_T] (K), p_nodes[n_p] (bar); axis wl_hi[n_hi] (µm, strictly ascending).
+ * Constants: c2 = H C / K_B, m = mass_amu AMU (frei_amd/constants.py).  nu_i = 1e4 / wl_hi[i] is
+ * formed on the host and uploaded.
+ *
+ * Per (T node t, line l), on the host in the C++ runtime (fp64, in this order):
+ *   S     = ((S_ref q_ratio[t]) exp(-(c2 E_low) (1/T - 1/T_ref)))
+ *           (expm1(-(c2 nu0) / T) / expm1(-(c2 nu0) / T_ref))
+ *   alpha = nu0 sqrt(((2 K_B) T) / m) / C                 (Doppler 1/e half-width)
+ *   gT    = gamma_ref exp(n_exp ln(T_ref / T))            (ln(T_ref / T) once per node)
+ *   A = S / (alpha sqrt(pi)),  1 / alpha,  gT / alpha
+ * Per pressure node: y = (gT / alpha) p.  Per axis point: x = |nu_i - nu0| (1 / alpha),
+ * K(x, y) = Re w(x + iy) (Faddeeva; relative error <= 2^-26 for x in [0, 1e6], y in [1e-8, 1e5];
+ * the algorithm is in frei_amd/csrc/frei_lines.hip) and
+ *   values[t][p][i] = float32((1 / m) sum_l A_l K(x, y))        (cm^2 g^-1, as kappa reads tables)
+ * over exactly the lines with |nu_i - nu0_l| <= cutoff (compared in fp64 on the uploaded nu_i),
+ * in ascending line index, accumulated in fp64 and rounded once: the result does not depend on
+ * how the axis, the nodes or the lines are blocked.  A point no line reaches is exactly 0.
+ *
+ * Not modelled: pressure shift, self-broadening, sub-Lorentzian wings, line mixing, continua,
+ * renormalisation of the truncated wing, and y = 0 (gamma_ref and p must be positive).
+ *
+ * Every argument error is found on the host before any device call and names the first
+ * offending index: null pointers, n_line < 1, unsorted nu0, non-finite values, S_ref < 0,
+ * gamma_ref <= 0, nu0 <= 0, mass_amu <= 0, T_ref <= 0, cutoff <= 0, q_ratio <= 0, T <= 0, p <= 0,
+ * a non-ascending axis.  *kernel_ms (may be NULL) receives the HIP-event time of the main kernel.
+ */
+int frei_xsec_create_lines(frei_xsec** out, int device, int64_t n_line, const double* nu0,
+                           const double* S_ref, const double* E_low, const double* gamma_ref,
+                           const double* n_exp, double mass_amu, double T_ref, double cutoff,
+                           const double* q_ratio, int n_T, int n_p, int64_t n_hi,
+                           const double* T_nodes, const double* p_nodes, const double* wl_hi,
+                           double* kernel_ms);
+/* Reads back points [lo, lo + n) of row (t, p) of any cross-section (uploaded, synthetic or
+ * from lines) into out[n]. */
+int frei_xsec_values(frei_xsec* x, int t, int p, int64_t lo, int64_t n, float* out);
+/*
  * binned_opacity for this species onto a grid: bins wl_bins[n_bins+1] (µm, ascending) with
  * centres lam[n_bins] (µm).  Target nodes T_nodes[n_T] (K) x p_nodes[n_p] (bar) each take
  * the nearest source node (xarray interp 'nearest', extrapolating; opacity.py:26-29).
