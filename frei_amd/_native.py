@@ -110,6 +110,12 @@ SIGNATURES = {
     "frei_set_table_binned": (ctypes.c_int, [_vp, ctypes.c_int, _vp, ctypes.c_int, _dp, _dp,
                                              _i64, _i64, _dp, ctypes.c_int, _dp,
                                              ctypes.c_int]),
+    "frei_xsec_mix": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.POINTER(_vp), _dp,
+                                     _dp]),
+    "frei_xsec_kdist": (ctypes.c_int, [_vp, _dp, _i64, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp,
+                                       ctypes.c_int, _dp, ctypes.POINTER(_i64)]),
+    "frei_set_table_kdist": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, _i64, ctypes.c_int, _dp,
+                                            _dp, ctypes.c_int, _dp, ctypes.c_int, _i64]),
     "frei_sspec_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _dp, ctypes.c_int,
                                          _i64, _dp]),
     "frei_sspec_bin": (ctypes.c_int, [_vp, _dp, _i64, ctypes.c_int, _dp,

@@ -17,7 +17,7 @@ from . import _native as N
 from .chemistry import ChemistryTable, chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, SIGMA_SB, UM
 from .emergent import emergent_call, pick
-from .engine import EMIT, Engine, f_toa, planck_prefactor, trapz_weights
+from .engine import EMIT, Engine, f_toa, planck_prefactor, quadrature_weights
 from .opacity import sigma_scattering
 from .transit import default_radius, level_radii, transit_call
 from .units import scalar, value
@@ -76,10 +76,13 @@ class BatchEngine:
     uploaded once).  The device re-interpolates each atmosphere's table at its own layer
     temperatures every sweep (frei_set_chemistry_batch) and the species sum stays in the sweep.
     Consecutive atmospheres in the same T brackets share table rows in the tiled sweep
-    (``FREI_ATM_TILE``), so order such a batch by temperature."""
+    (``FREI_ATM_TILE``), so order such a batch by temperature.
+
+    ``quad_weights`` (cm, one per column) replaces the trapezoid weights of the bolometric sums, as
+    in :class:`~frei_amd.engine.Engine` (a k-distribution's columns, ``KGrid.col_weights``)."""
 
     def __init__(self, lam_um, p_bar, opacities, g, mmr=None, m_bar=M_BAR_DEFAULT, F_toa=None,
-                 device=0):
+                 device=0, quad_weights=None):
         lib = N.lib()
         self.lam_um = np.asarray(value(lam_um, "um"), dtype=float)
         self.p_bar = np.asarray(value(p_bar, "bar"), dtype=float)
@@ -99,7 +102,7 @@ class BatchEngine:
         if ft.ndim == 2:     # one F_TOA per atmosphere (planets around different stars)
             ft_atm = N.f64(np.broadcast_to(ft, (self.n_atm, self.n_lam)))
             ft = N.f64(ft_atm[0])
-        wtr = N.f64(trapz_weights(lam_cm))
+        wtr = N.f64(quadrature_weights(lam_cm, quad_weights))
         p_cgs = N.f64(self.p_bar * BAR)
         ctx = ctypes.c_void_p()
         N.check(lib.frei_ctx_create_batch(ctypes.byref(ctx), device, self.n_layers, self.n_lam,
@@ -504,6 +507,11 @@ def batched_emission_spectra(grids, n_timesteps=1, n_zero_crossings=2, convergen
     :class:`BatchResult` of :class:`BatchRecord` (spectrum, final_T, n_iter, temp_hist, T_eff,
     T_milne, T_planck) that keeps the engine for ``contribution(m)`` and ``dtaus(m)``."""
     from .core import F_TOA, Spectrum
+    if any(hasattr(gr, "col_weights") for gr in grids):
+        raise NotImplementedError(
+            "batched_emission_spectra given KGrids: it would sum the columns of a k-distribution "
+            "with trapezoid weights; build BatchEngine(col_lam, ..., quad_weights=col_weights) "
+            "directly")
     g0 = grids[0]
     for gr in grids[1:]:
         if not (np.array_equal(gr.lam, g0.lam) and np.array_equal(gr.pressures, g0.pressures)):

@@ -8,7 +8,10 @@ uploaded once per device and stays in HBM; K6 (``frei_amd/csrc/frei_binning.hip`
 it onto a Grid's wavelength bins and selects the nearest source (T, p) node for every
 grid node.  ``binned_opacity`` returns :class:`BinnedTable` objects: the Engine bins them
 straight into its device tables (no host round trip); ``.values`` materialises the
-(pressure, temperature, wavelength) array on the host when asked.
+(pressure, temperature, wavelength) array on the host when asked.  K18
+(``frei_amd/csrc/frei_kdist.hip``) gives a second road from the same resident values:
+``CrossSection.mix`` premixes species, ``CrossSection.kdist`` and :class:`KTable` sort every bin
+into a k-distribution (``frei_amd.kdist`` holds the grid that runs on it).
 """
 import ctypes
 import glob
@@ -20,7 +23,7 @@ from . import _native as N
 from .chemistry import iso_to_species
 from .units import value
 
-__all__ = ["CrossSection", "BinnedTable", "binned_opacity", "open_cross_section",
+__all__ = ["CrossSection", "BinnedTable", "KTable", "binned_opacity", "open_cross_section",
            "GROUPIES", "EXACT"]
 
 GROUPIES, EXACT = 0, 1
@@ -64,6 +67,34 @@ class CrossSection:
         obj._synthetic = None
         obj._lines = make
         return obj
+
+    @classmethod
+    def mix(cls, sources, weights, isotopologue="mix", device=0):
+        """The premixed cross-section ``sum_s weights[s] * sources[s]`` of CrossSections on
+        shared nodes and one axis, computed on ``device`` (frei_xsec_mix, K18).  ``weights``
+        (mass mixing ratios at the sources' own nodes) broadcasts to (n_src, n_T, n_p).  A
+        k-distribution needs the mixture: the k(g) of several species do not add.  The result
+        holds no host copy (``.opacity`` is None); ``.values()`` downloads it."""
+        sources = list(sources)
+        if not sources:
+            raise ValueError("CrossSection.mix needs at least one source")
+        s0 = sources[0]
+        w = N.f64(np.broadcast_to(np.asarray(weights, dtype=float),
+                                  (len(sources), s0.temperature.size, s0.pressure.size)))
+        timing = {}
+
+        def make(dev):
+            h, ms = ctypes.c_void_p(), ctypes.c_double(0.0)
+            src = (ctypes.c_void_p * len(sources))(*[x.handle(dev).value for x in sources])
+            N.check(N.lib().frei_xsec_mix(ctypes.byref(h), len(sources), src, N.dptr(w),
+                                          ctypes.byref(ms)))
+            timing[dev] = ms.value
+            return h
+
+        xs = cls._from_lines(make, s0.temperature, s0.pressure, s0.wavelength, isotopologue)
+        xs.handle(device)
+        xs.kernel_ms = timing[device]     # HIP-event time of the kernel
+        return xs
 
     def handle(self, device=0):
         """frei_xsec* of this cross-section on ``device`` (uploaded once)."""
@@ -110,6 +141,24 @@ class CrossSection:
                                       N.dptr(wl_bins), N.dptr(lam), lam.size, N.dptr(T), T.size,
                                       N.dptr(p), p.size, N.dptr(res)))
         return res
+
+    def kdist(self, wl_bins, g, temperatures, pressures, device=0, out=True):
+        """The k-distribution (frei_xsec_kdist, K18; the definition is in include/frei_hip.h):
+        per bin of ``wl_bins`` (µm) the values sorted ascending and sampled at the quadrature
+        points ``g`` (each in (0, 1)) -> (k[pressure][temperature][bin][g], counts[bin]), the
+        points per bin (``out=False``: k stays on the device, for timing, and is None)."""
+        wl_bins = N.f64(value(wl_bins, "um"))
+        g = N.f64(np.atleast_1d(g))
+        T = N.f64(np.atleast_1d(value(temperatures, "K")))
+        p = N.f64(np.atleast_1d(value(pressures, "bar")))
+        n_bins = wl_bins.size - 1
+        res = np.empty((p.size, T.size, n_bins, g.size)) if out else None
+        counts = np.zeros(max(n_bins, 0), dtype=np.int64)
+        N.check(N.lib().frei_xsec_kdist(
+            self.handle(device), N.dptr(wl_bins), n_bins, g.size, N.dptr(g), N.dptr(T), T.size,
+            N.dptr(p), p.size, N.dptr(res),
+            counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return res, counts
 
     def values(self, t=None, p=None, device=0):
         """The resident float32 values read back from ``device`` (frei_xsec_values): the whole
@@ -167,6 +216,61 @@ class BinnedTable:
             self._values = self.xsec.bin(self.wl_bins, self.wavelength, self.temperature,
                                          self.pressure, self.groupies, self.device)
         return self._values
+
+
+class KTable:
+    """A cross-section's k-distribution on a grid's bins (K18): nodes ``pressure`` (bar) x
+    ``temperature`` (K), and per bin of ``wl_bins`` (µm) one column per quadrature point of
+    ``g``, column ``b * n_g + q`` for bin b at g_q; ``wavelength`` repeats each bin's centre
+    n_g times.  The Engine writes it directly into HBM (frei_set_table_kdist)."""
+
+    dims = ("pressure", "temperature", "wavelength")
+
+    def __init__(self, xsec, wl_bins, g, temperatures, pressures, device=0):
+        self.xsec = xsec
+        self.wl_bins = N.f64(value(wl_bins, "um"))
+        self.g = N.f64(np.atleast_1d(g))
+        self.temperature = N.f64(np.atleast_1d(value(temperatures, "K")))
+        self.pressure = N.f64(np.atleast_1d(value(pressures, "bar")))
+        self.wavelength = np.repeat((self.wl_bins[:-1] + self.wl_bins[1:]) / 2, self.g.size)
+        self.device = device
+        self._values = None
+        self._counts = None
+
+    @property
+    def n_bins(self):
+        return self.wl_bins.size - 1
+
+    @property
+    def shape(self):
+        return (self.pressure.size, self.temperature.size, self.wavelength.size)
+
+    @property
+    def values(self):
+        """(pressure, temperature, n_bins * n_g) on the host."""
+        if self._values is None:
+            v, _ = self.xsec.kdist(self.wl_bins, self.g, self.temperature, self.pressure,
+                                   self.device)
+            self._values = v.reshape(self.shape)
+        return self._values
+
+    @property
+    def counts(self):
+        """Points of the cross-section's axis per bin (host arithmetic on the axis alone;
+        ``CrossSection.kdist`` returns the device call's own)."""
+        if self._counts is None:
+            self._counts = bin_counts(self.xsec.wavelength, self.wl_bins)
+        return self._counts
+
+
+def bin_counts(wavelength, wl_bins):
+    """Points per bin under K6's membership (pandas.cut right-closed on the cropped axis): bin k
+    holds ``wl_bins[k] < wl <= wl_bins[k + 1]``, the last bin ``wl < wl_bins[-1]``."""
+    wl, b = np.asarray(wavelength, dtype=float), np.asarray(wl_bins, dtype=float)
+    start = np.searchsorted(wl, b[:-1], side="right")
+    end = np.searchsorted(wl, b[1:], side="right")
+    end[-1] = np.searchsorted(wl, b[-1], side="left")
+    return np.maximum(end - start, 0).astype(np.int64)
 
 
 def open_cross_section(path):

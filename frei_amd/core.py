@@ -277,6 +277,10 @@ def effective_temperature_milne(grid, spec, dtaus, final_temps):
     """Photosphere temperature from Milne's tau ~ 2/3 (core.py:386-405).  The per-wavelength
     np.interp over layers runs on the GPU (frei_milne_pressure); the weighted mean and the
     final interpolation are O(n_lambda) host work, as in the reference."""
+    if hasattr(grid, "col_weights"):
+        raise NotImplementedError(
+            "effective_temperature_milne on a KGrid: the Milne mean weights wavelengths, not the "
+            "columns of a k-distribution (bin width x quadrature weight); not implemented yet")
     lam = np.asarray(grid.lam)
     p = np.asarray(grid.pressures)
     eng, d = _post_engine(grid, dtaus)

@@ -282,7 +282,12 @@ __global__ void gen_xsec_kernel(float* __restrict__ x, int nT, int np, int64_t n
           (float)(base * sqrt(T[a] / 1000.0) * pow(p[b], 0.05));
 }
 
+}  // namespace
+
 // ------------------------------------------------------------------- host plan
+// (namespace frei: K18, frei_kdist.hip, shares the parts that define which points a bin holds
+// and which source row a target node reads; frei_host.h declares them)
+namespace frei {
 // scipy interp1d 'nearest' after xarray sortby: midpoints x[i]/2 + x[i+1]/2, searchsorted
 // side='left', clipped (opacity.py:26-29 interp_kwargs, fill_value='extrapolate').
 std::vector<int> nearest_index(const std::vector<double>& nodes, const double* t, int n) {
@@ -299,6 +304,59 @@ std::vector<int> nearest_index(const std::vector<double>& nodes, const double* t
   }
   return out;
 }
+
+// pandas.cut(right=True) ranges [start_k, end_k) of bin k = (b_k, b_{k+1}] on the cropped axis
+// b_0 < x < b_last (opacity.py:131-135, interp.py:289), wl ascending.
+void bin_ranges(const std::vector<double>& wl, const double* wl_bins, int64_t n_bins,
+                std::vector<int64_t>* start, std::vector<int64_t>* end) {
+  start->resize(n_bins);
+  end->resize(n_bins);
+  for (int64_t k = 0; k < n_bins; ++k) {
+    (*start)[k] = std::upper_bound(wl.begin(), wl.end(), wl_bins[k]) - wl.begin();
+    (*end)[k] = (k + 1 < n_bins ? std::upper_bound(wl.begin(), wl.end(), wl_bins[k + 1])
+                                : std::lower_bound(wl.begin(), wl.end(), wl_bins[k + 1])) -
+                wl.begin();
+    (*end)[k] = std::max((*end)[k], (*start)[k]);
+  }
+}
+
+// The nearest source node of every target node (kp, kt), the distinct source rows they select
+// (ascending source order) and, per distinct row, the destination rows that read it (CSR);
+// dest_off[kp * n_T + kt] is the element offset of the target node's row in the output.
+SourceRows source_rows(const frei_xsec* x, const double* T_t, int n_T, const double* p_t, int n_p,
+                       const std::vector<int64_t>& dest_off) {
+  const std::vector<int> ti = nearest_index(x->T, T_t, n_T);
+  const std::vector<int> pi = nearest_index(x->p, p_t, n_p);
+  std::map<int64_t, int> uid;  // source row -> unique index (ascending source order)
+  for (int kp = 0; kp < n_p; ++kp)
+    for (int kt = 0; kt < n_T; ++kt) uid[(int64_t)ti[kt] * x->np + pi[kp]] = 0;
+  SourceRows r;
+  for (auto& kv : uid) {
+    kv.second = (int)r.row_off.size();
+    r.row_off.push_back(kv.first * x->nhi);
+  }
+  const int U = (int)r.row_off.size();
+  std::vector<int32_t> dst_src(dest_off.size());
+  for (int kp = 0; kp < n_p; ++kp)
+    for (int kt = 0; kt < n_T; ++kt)
+      dst_src[(size_t)kp * n_T + kt] = uid[(int64_t)ti[kt] * x->np + pi[kp]];
+  r.fan_off.assign(U + 1, 0);
+  for (int32_t q : dst_src) r.fan_off[q + 1]++;
+  for (int u = 0; u < U; ++u) r.fan_off[u + 1] += r.fan_off[u];
+  r.fan_dst.resize(dst_src.size());
+  std::vector<int32_t> fill(r.fan_off.begin(), r.fan_off.end() - 1);
+  for (size_t d = 0; d < dst_src.size(); ++d) r.fan_dst[fill[dst_src[d]]++] = dest_off[d];
+  return r;
+}
+
+int check_ascending(const double* a, int64_t n, const char* what) {
+  for (int64_t i = 0; i + 1 < n; ++i)
+    if (!(a[i + 1] > a[i])) return set_error(std::string(what) + " must be strictly ascending");
+  return 0;
+}
+}  // namespace frei
+
+namespace {
 
 // numpy pairwise summation (np.mean of the group wavelengths, opacity.py:42).
 double pairwise_sum(const double* a, int64_t n) {
@@ -328,12 +386,6 @@ struct Dest {
   std::vector<int64_t> off;  // [n_p * n_T] row-major over (kp, kt)
 };
 
-int check_ascending(const double* a, int64_t n, const char* what) {
-  for (int64_t i = 0; i + 1 < n; ++i)
-    if (!(a[i + 1] > a[i])) return set_error(std::string(what) + " must be strictly ascending");
-  return 0;
-}
-
 // The whole binning of one species into device buffer `out` (rows at dest.off).
 int bin_into(frei_xsec* x, int mode, const double* wl_bins, const double* lam, int64_t n_bins,
              int64_t lam_lo, int64_t n_out, const double* T_t, const double* p_t,
@@ -345,40 +397,14 @@ int bin_into(frei_xsec* x, int mode, const double* wl_bins, const double* lam, i
   hipStream_t st = x->stream;
   const std::vector<double>& wl = x->wl;
   // pandas.cut(right=True) ranges on the cropped axis b_0 < x < b_last
-  std::vector<int64_t> start(n_bins), end(n_bins);
-  for (int64_t k = 0; k < n_bins; ++k) {
-    start[k] = std::upper_bound(wl.begin(), wl.end(), wl_bins[k]) - wl.begin();
-    end[k] = (k + 1 < n_bins ? std::upper_bound(wl.begin(), wl.end(), wl_bins[k + 1])
-                             : std::lower_bound(wl.begin(), wl.end(), wl_bins[k + 1])) -
-             wl.begin();
-    end[k] = std::max(end[k], start[k]);
-  }
-  // nearest source nodes and the unique source rows they select
-  const std::vector<int> ti = nearest_index(x->T, T_t, dest.n_T);
-  const std::vector<int> pi = nearest_index(x->p, p_t, dest.n_p);
-  std::map<int64_t, int> uid;  // source row -> unique index (ascending source order)
-  for (int kp = 0; kp < dest.n_p; ++kp)
-    for (int kt = 0; kt < dest.n_T; ++kt) uid[(int64_t)ti[kt] * x->np + pi[kp]] = 0;
-  std::vector<int64_t> row_off;
-  for (auto& kv : uid) {
-    kv.second = (int)row_off.size();
-    row_off.push_back(kv.first * x->nhi);
-  }
+  std::vector<int64_t> start, end;
+  bin_ranges(wl, wl_bins, n_bins, &start, &end);
+  // nearest source nodes, the unique source rows they select and their fan-out
+  const SourceRows sr = source_rows(x, T_t, dest.n_T, p_t, dest.n_p, dest.off);
+  const std::vector<int64_t>& row_off = sr.row_off;
+  const std::vector<int32_t>& fan_off = sr.fan_off;
+  const std::vector<int64_t>& fan_dst = sr.fan_dst;
   const int U = (int)row_off.size();
-  std::vector<int32_t> dst_src(dest.off.size());
-  for (int kp = 0; kp < dest.n_p; ++kp)
-    for (int kt = 0; kt < dest.n_T; ++kt)
-      dst_src[(size_t)kp * dest.n_T + kt] = uid[(int64_t)ti[kt] * x->np + pi[kp]];
-
-  // fan-out: destination rows of every unique source row (CSR)
-  std::vector<int32_t> fan_off(U + 1, 0);
-  for (int32_t q : dst_src) fan_off[q + 1]++;
-  for (int u = 0; u < U; ++u) fan_off[u + 1] += fan_off[u];
-  std::vector<int64_t> fan_dst(dst_src.size());
-  {
-    std::vector<int32_t> fill(fan_off.begin(), fan_off.end() - 1);
-    for (size_t d = 0; d < dst_src.size(); ++d) fan_dst[fill[dst_src[d]]++] = dest.off[d];
-  }
 
   // (the host vectors outlive every copy: the stream is synchronised before returning, on every
   // path once a plan copy may be in flight, so the next call's stage_reserve never frees or
@@ -536,11 +562,11 @@ int bin_into_table(frei_xsec* x, int mode, const double* wl_bins, const double* 
 }
 }  // namespace frei
 
-// ==================================================================== C ABI
-extern "C" {
-
-static int xsec_alloc(frei_xsec** out, int device, int n_T, int n_p, int64_t n_hi,
-                      const double* T_nodes, const double* p_nodes, const double* wl_hi) {
+namespace frei {
+// A cross-section on `device` with its nodes and axis set and its values allocated, not yet
+// written (frei_xsec_mix, frei_kdist.hip, fills one too).
+int xsec_alloc(frei_xsec** out, int device, int n_T, int n_p, int64_t n_hi,
+               const double* T_nodes, const double* p_nodes, const double* wl_hi) {
   if (!out || !T_nodes || !p_nodes || !wl_hi) return set_error("null argument");
   *out = nullptr;
   if (n_T < 1 || n_p < 1 || n_hi < 2) return set_error("empty cross-section grid");
@@ -562,6 +588,10 @@ static int xsec_alloc(frei_xsec** out, int device, int n_T, int n_p, int64_t n_h
   *out = x;
   return 0;
 }
+}  // namespace frei
+
+// ==================================================================== C ABI
+extern "C" {
 
 int frei_xsec_create(frei_xsec** out, int device, const float* values, int n_T, int n_p,
                      int64_t n_hi, const double* T_nodes, const double* p_nodes,

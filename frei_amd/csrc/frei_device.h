@@ -603,5 +603,11 @@ int bin_into_table(frei_xsec* x, int mode, const double* wl_bins, const double* 
                    int64_t n_bins, int64_t lam_lo, int64_t n_out, const double* T_t, int n_T,
                    const double* p_t, int n_p, const int64_t* row_off, double* d_tab,
                    int device);
+// K18 (frei_kdist.hip): columns [col_lo, col_lo + n_out) of one species' k-distribution
+// (n_bins * n_g columns) into table rows d_tab + row_off[kp * n_T + kt].
+int kdist_into_table(frei_xsec* x, const double* wl_bins, int64_t n_bins, int n_g,
+                     const double* g, int64_t col_lo, int64_t n_out, const double* T_t, int n_T,
+                     const double* p_t, int n_p, const int64_t* row_off, double* d_tab,
+                     int device);
 
 }  // namespace frei

@@ -1764,6 +1764,20 @@ int frei_set_table_separable(frei_ctx* c, int s, const double* base, const doubl
   return scan_nan(c, s);
 }
 
+// Element offset in species s's table of the row of target node (kp, kt), [n_p * n_T]: the T
+// axis is stored ascending (the device binning calls write their rows there).
+static std::vector<int64_t> node_row_offsets(frei_ctx* c, int s, const double* T_nodes, int n_T,
+                                             int n_p) {
+  const std::vector<int32_t> perm = t_order(T_nodes, n_T);
+  std::vector<int32_t> rank(n_T);
+  for (int t = 0; t < n_T; ++t) rank[perm[t]] = t;
+  std::vector<int64_t> row_off((size_t)n_p * n_T);
+  for (int kp = 0; kp < n_p; ++kp)
+    for (int kt = 0; kt < n_T; ++kt)
+      row_off[(size_t)kp * n_T + kt] = ((int64_t)kp * n_T + rank[kt]) * c->sp[s].stride;
+  return row_off;
+}
+
 int frei_set_table_binned(frei_ctx* c, int s, frei_xsec* x, int mode, const double* wl_bins,
                           const double* lam, int64_t n_bins, int64_t lam_lo,
                           const double* T_nodes, int n_T, const double* p_nodes, int n_p) {
@@ -1772,16 +1786,23 @@ int frei_set_table_binned(frei_ctx* c, int s, frei_xsec* x, int mode, const doub
   std::vector<double> p_cgs(n_p > 0 ? n_p : 0);
   for (int k = 0; k < n_p; ++k) p_cgs[k] = p_nodes[k] * 1e6;  // bar -> dyn cm^-2
   TRY(set_table_common(c, s, p_cgs.data(), n_p, T_nodes, n_T));
-  // destination row of node (kp, kt): the T axis is stored ascending
-  const std::vector<int32_t> perm = t_order(T_nodes, n_T);
-  std::vector<int32_t> rank(n_T);
-  for (int t = 0; t < n_T; ++t) rank[perm[t]] = t;
-  std::vector<int64_t> row_off((size_t)n_p * n_T);
-  for (int kp = 0; kp < n_p; ++kp)
-    for (int kt = 0; kt < n_T; ++kt)
-      row_off[(size_t)kp * n_T + kt] = ((int64_t)kp * n_T + rank[kt]) * c->sp[s].stride;
+  const std::vector<int64_t> row_off = node_row_offsets(c, s, T_nodes, n_T, n_p);
   TRY(bin_into_table(x, mode, wl_bins, lam, n_bins, lam_lo, c->nlam, T_nodes, n_T, p_nodes,
                      n_p, row_off.data(), c->sp[s].d_tab, c->device));
+  return scan_nan(c, s);
+}
+
+int frei_set_table_kdist(frei_ctx* c, int s, frei_xsec* x, const double* wl_bins, int64_t n_bins,
+                         int n_g, const double* g, const double* T_nodes, int n_T,
+                         const double* p_nodes, int n_p, int64_t col_lo) {
+  if (!c || !x || !wl_bins || !g || !T_nodes || !p_nodes) return fail("null argument");
+  TRY(set_device(c));
+  std::vector<double> p_cgs(n_p > 0 ? n_p : 0);
+  for (int k = 0; k < n_p; ++k) p_cgs[k] = p_nodes[k] * 1e6;  // bar -> dyn cm^-2
+  TRY(set_table_common(c, s, p_cgs.data(), n_p, T_nodes, n_T));
+  const std::vector<int64_t> row_off = node_row_offsets(c, s, T_nodes, n_T, n_p);
+  TRY(kdist_into_table(x, wl_bins, n_bins, n_g, g, col_lo, c->nlam, T_nodes, n_T, p_nodes, n_p,
+                       row_off.data(), c->sp[s].d_tab, c->device));
   return scan_nan(c, s);
 }
 

@@ -171,12 +171,6 @@ int wave_group(double mean_points) {
 #endif
 }
 
-int check_ascending(const double* a, int64_t n, const char* what) {
-  for (int64_t i = 0; i + 1 < n; ++i)
-    if (!(a[i + 1] > a[i])) return set_error(std::string(what) + " must be strictly ascending");
-  return 0;
-}
-
 template <typename T>
 int grow(T** p, size_t* cap, size_t n) {
   if (*cap >= n) return 0;

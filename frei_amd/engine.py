@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import _native as N
-from .binning import BinnedTable
+from .binning import BinnedTable, KTable
 from .chemistry import ChemistryTable, fixed_provider_mmr, provider_mmr
 from .chemistry import chemistry as mock_chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, UM
@@ -47,6 +47,19 @@ def trapz_weights(lam_cm):
     w = np.zeros(lam_cm.size)
     w[:-1] += d / 2
     w[1:] += d / 2
+    return w
+
+
+def quadrature_weights(lam_cm, quad_weights=None):
+    """The per-column weights (cm) of the bolometric sums on the global grid: ``quad_weights``
+    when given (a k-distribution's columns carry bin width x quadrature weight, ``KGrid``), else
+    the trapezoid weights of ``lam_cm``."""
+    if quad_weights is None:
+        return trapz_weights(lam_cm)
+    w = np.asarray(value(quad_weights, "cm"), dtype=float)
+    if w.shape != lam_cm.shape:
+        raise ValueError(f"quad_weights must be one weight per grid column {lam_cm.shape}, "
+                         f"got shape {w.shape}")
     return w
 
 
@@ -107,11 +120,13 @@ class Engine:
     :class:`~frei_amd.chemistry.ChemistryTable` (T-dependent, re-evaluated every sweep), or
     ``chemistry``: a provider on the reference's signature ``chemistry(T, p, species,
     m_bar=...)`` (frei_amd.chemistry, "chemistry providers"), evaluated where the reference's
-    kappa evaluates it.
+    kappa evaluates it.  ``quad_weights`` (cm, one per column of the global grid) replaces the
+    trapezoid weights of the bolometric sums (default None: ``trapz_weights(lam_cm)``).
     """
 
     def __init__(self, lam_um, p_bar, opacities, g=2478.6519476149147, m_bar=M_BAR_DEFAULT,
-                 F_toa=None, mmr=None, device=0, lam_slice=None, comm=None, chemistry=None):
+                 F_toa=None, mmr=None, device=0, lam_slice=None, comm=None, chemistry=None,
+                 quad_weights=None):
         lib = N.lib()
         self.lam_um = np.asarray(value(lam_um, "um"), dtype=float)
         self.p_bar = np.asarray(value(p_bar, "bar"), dtype=float)
@@ -131,7 +146,7 @@ class Engine:
         self.sigma = N.f64(sigma_scattering(self.lam_um, self.m_bar)[sl])
         ft = f_toa(self.lam_um) if F_toa is None else value(F_toa, "erg / (s cm3)")
         self.f_toa = N.f64(np.asarray(ft, dtype=float)[sl])
-        self.wtr = N.f64(trapz_weights(lam_cm)[sl])
+        self.wtr = N.f64(quadrature_weights(lam_cm, quad_weights)[sl])
         self.p_cgs = N.f64(self.p_bar * BAR)
         ctx = ctypes.c_void_p()
         N.check(lib.frei_ctx_create(ctypes.byref(ctx), device, self.n_layers, self.n_lam,
@@ -233,6 +248,14 @@ class Engine:
                 self._ctx, s, tab.xsec.handle(self.device), tab.mode, N.dptr(tab.wl_bins),
                 N.dptr(tab.wavelength), tab.wavelength.size, self.lo, N.dptr(tab.temperature),
                 tab.temperature.size, N.dptr(tab.pressure), tab.pressure.size))
+            return
+        if isinstance(tab, KTable):
+            if tab.wavelength.size != self.lam_um.size:
+                raise ValueError("k-table columns (n_bins * n_g) must match the grid's columns")
+            N.check(lib.frei_set_table_kdist(
+                self._ctx, s, tab.xsec.handle(self.device), N.dptr(tab.wl_bins), tab.n_bins,
+                tab.g.size, N.dptr(tab.g), N.dptr(tab.temperature), tab.temperature.size,
+                N.dptr(tab.pressure), tab.pressure.size, self.lo))
             return
         if isinstance(tab, SeparableTable):
             N.check(lib.frei_set_table_separable(

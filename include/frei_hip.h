@@ -524,6 +524,60 @@ int frei_set_table_binned(frei_ctx* ctx, int s, frei_xsec* x, int mode, const do
                           const double* T_nodes, int n_T, const double* p_nodes, int n_p);
 
 /*
+ * K18: correlated-k tables (no reference counterpart; HELIOS-K gives its line-by-line calculator
+ * this second output for HELIOS).
+ *
+ * Premix.  out = a new cross-section on the sources' device, nodes and axis with
+ *   out[t][p][i] = float32(acc),  acc = +0.0, then for s = 0 .. n_src - 1 in this order
+ *   acc = acc + weight[s][t][p] * double(src_s[t][p][i])       (the product rounded, then the sum)
+ * weight[n_src][n_T][n_p] are the mass mixing ratios at the sources' own nodes.  The result is an
+ * ordinary frei_xsec: K6 bins it, frei_xsec_values reads it back, frei_xsec_destroy frees it; the
+ * sources stay as they are.  Correlated-k needs it: adding the k(g) of several species at equal g
+ * would treat their lines as perfectly correlated, so the mixture is sorted, not the species.
+ * Errors, all found on the host before any device call, each naming the first offender:
+ * n_src < 1, a null source, sources on different devices, sources whose T_nodes, p_nodes or wl_hi
+ * are not element for element equal, a weight that is not finite or is negative.  *kernel_ms (may
+ * be NULL) receives the HIP-event time of the kernel.
+ */
+int frei_xsec_mix(frei_xsec** out, int n_src, frei_xsec* const* src, const double* weight,
+                  double* kernel_ms);
+/*
+ * The k-distribution of x on bins wl_bins[n_bins + 1] (µm, strictly ascending) at the quadrature
+ * points g[n_g] (each finite and in (0, 1), any order; 1 <= n_g <= 64), for target nodes
+ * T_nodes[n_T] (K) x p_nodes[n_p] (bar).  out[n_p][n_T][n_bins][n_g] float64 on the host (NULL:
+ * leave the result on the device, for timing); counts[n_bins] (may be NULL) receives the points
+ * per bin.
+ *
+ * Bin membership is K6's: bin k holds the points wl_bins[k] < wl <= wl_bins[k + 1], the last bin
+ * wl < wl_bins[n_bins] (pandas.cut right-closed on the cropped axis).  Every target node takes
+ * its nearest source node as in frei_xsec_bin, and target nodes that select one source row get
+ * the same values.  Per (source row, bin) with n points:
+ *   the float32 values, with -0 made +0 and every NaN the canonical quiet NaN, are sorted
+ *   ascending with NaN last (np.sort's order): s_0 ... s_{n-1};
+ *   per g_q the plan, on the host in the C++ runtime in fp64:
+ *     t = g_q n - 0.5,  j = clamp(floor(t), 0, n - 2),  f = clamp(t - j, 0, 1);
+ *   k = double(s_j) + f (double(s_{j+1}) - double(s_j)), unfused;
+ *   n = 1: k = double(s_0);  n = 0: k = NaN.
+ * A bin of more than 32768 points is an error that names the bin and its count, and nothing is
+ * launched: a bin's keys are sorted in LDS (32768 float32 keys are 128 KiB of the 160 KiB); a
+ * merge pass for wider bins is out of scope.  Every argument error is found before any device
+ * call.  Two kernel forms, chosen by bin size, give the same bits (frei_kdist.hip;
+ * FREI_KDIST_FORM = auto, block or wave selects one for diagnostics).  Timing: frei_xsec_timing.
+ */
+int frei_xsec_kdist(frei_xsec* x, const double* wl_bins, int64_t n_bins, int n_g, const double* g,
+                    const double* T_nodes, int n_T, const double* p_nodes, int n_p, double* out,
+                    int64_t* counts);
+/*
+ * The same k-distribution written straight into species s of a context, as
+ * frei_set_table_binned does: the context's n_lam columns are [col_lo, col_lo + n_lam) of the
+ * n_bins * n_g columns (column b * n_g + q is bin b at g_q); the table gets nodes p_nodes (bar) x
+ * T_nodes (K).
+ */
+int frei_set_table_kdist(frei_ctx* ctx, int s, frei_xsec* x, const double* wl_bins, int64_t n_bins,
+                         int n_g, const double* g, const double* T_nodes, int n_T,
+                         const double* p_nodes, int n_p, int64_t col_lo);
+
+/*
  * Stellar spectrum binning (phoenix.py:13-17, 43-52).  A frei_sspec is a library of model
  * spectra on one shared wavelength axis: flux[n_spec][n_hi] float64 resident in HBM on
  * wl_hi[n_hi] (um, strictly ascending).
