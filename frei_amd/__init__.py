@@ -6,7 +6,8 @@ species-summed opacity assembly, radiative-equilibrium T-P loop): the public nam
 (``frei_amd/csrc``) behind the C ABI of ``include/frei_hip.h``.
 """
 from .batch import BatchEngine, BatchRecord, BatchResult, batched_emission_spectra
-from .binning import BinnedTable, CrossSection, KTable, open_cross_section
+from .binning import (BinnedTable, CrossSection, KLibrary, KTable, MixedKTable,
+                      open_cross_section)
 from .chemistry import ChemistryTable, chemistry, iso_to_mass, iso_to_species
 from .core import (B_star, F_TOA, Grid, Planet, Spectrum, contribution_function,
                    effective_temperature,

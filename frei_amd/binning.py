@@ -11,7 +11,9 @@ straight into its device tables (no host round trip); ``.values`` materialises t
 (pressure, temperature, wavelength) array on the host when asked.  K18
 (``frei_amd/csrc/frei_kdist.hip``) gives a second road from the same resident values:
 ``CrossSection.mix`` premixes species, ``CrossSection.kdist`` and :class:`KTable` sort every bin
-into a k-distribution (``frei_amd.kdist`` holds the grid that runs on it).
+into a k-distribution (``frei_amd.kdist`` holds the grid that runs on it).  K19
+(``frei_amd/csrc/frei_kmix.hip``) mixes species from their k-tables alone: a :class:`KLibrary`
+keeps the tables resident and folds them by random overlap into a :class:`MixedKTable`.
 """
 import ctypes
 import glob
@@ -23,8 +25,8 @@ from . import _native as N
 from .chemistry import iso_to_species
 from .units import value
 
-__all__ = ["CrossSection", "BinnedTable", "KTable", "binned_opacity", "open_cross_section",
-           "GROUPIES", "EXACT"]
+__all__ = ["CrossSection", "BinnedTable", "KTable", "KLibrary", "MixedKTable", "binned_opacity",
+           "open_cross_section", "fixed_point_weights", "GROUPIES", "EXACT"]
 
 GROUPIES, EXACT = 0, 1
 
@@ -261,6 +263,188 @@ class KTable:
         if self._counts is None:
             self._counts = bin_counts(self.xsec.wavelength, self.wl_bins)
         return self._counts
+
+
+def fixed_point_weights(weights):
+    """K19's fixed-point quadrature weights ``W_q = rint(w_q 2^30)`` (uint64; the definition is in
+    include/frei_hip.h): every w_q finite and positive, every W_q >= 1 and sum(W) <= 2^31."""
+    w = np.asarray(weights, dtype=float)
+    W, total = [], 0
+    for q, wq in enumerate(w):
+        if not np.isfinite(wq) or not wq > 0.0 or wq > 2.0:
+            raise ValueError(f"weights[{q}] = {wq} must be finite and positive, and the weights "
+                             "sum to at most 2")
+        W.append(int(np.rint(wq * 2.0 ** 30)))
+        if W[-1] < 1:
+            raise ValueError(f"weights[{q}] = {wq} is below the fixed-point step 2^-30")
+        total += W[-1]
+        if total > 2 ** 31:
+            raise ValueError(f"the weights up to weights[{q}] sum to more than 2")
+    return np.array(W, dtype=np.uint64)
+
+
+class KLibrary:
+    """Several species' k-tables on shared nodes, bins and one quadrature, resident on
+    ``device`` (frei_klib, K19).  ``tables`` is ``{name: CrossSection | array[n_p][n_T][n_bins]
+    [n_g]}``: a CrossSection is sorted on the device straight into its slot (K18's
+    k-distribution at the library's nodes, bins and ``g``), an array is uploaded.  ``wl_bins``
+    (µm) are the bin edges, ``g`` (strictly ascending in (0, 1)) and ``weights`` the quadrature,
+    ``temperatures`` (K) x ``pressures`` (bar) the nodes.  :meth:`mix` folds the species by
+    random overlap with resort-and-rebin (the definition is in include/frei_hip.h) for any
+    number of compositions; :meth:`table` gives the :class:`MixedKTable` an Engine takes.
+    Nothing touches the device before the first mix."""
+
+    def __init__(self, tables, wl_bins, g, weights, temperatures, pressures, device=0):
+        if not tables:
+            raise ValueError("KLibrary needs tables={name: CrossSection or array}")
+        self.names = list(tables)
+        self.wl_bins = N.f64(value(wl_bins, "um"))
+        self.g = N.f64(np.atleast_1d(g))
+        self.weights = N.f64(np.atleast_1d(weights))
+        self.temperature = N.f64(np.atleast_1d(value(temperatures, "K")))
+        self.pressure = N.f64(np.atleast_1d(value(pressures, "bar")))
+        if self.wl_bins.ndim != 1 or self.wl_bins.size < 2 or np.any(np.diff(self.wl_bins) <= 0):
+            raise ValueError("wl_bins must be strictly ascending bin edges of at least 1 bin")
+        if self.g.ndim != 1 or self.g.shape != self.weights.shape:
+            raise ValueError("g and weights must be 1-D arrays of one length")
+        if not 1 <= self.g.size <= 64:
+            raise ValueError(f"n_g = {self.g.size} lies outside [1, 64]")
+        for q, gq in enumerate(self.g):
+            if not (np.isfinite(gq) and 0.0 < gq < 1.0) or (q and not gq > self.g[q - 1]):
+                raise ValueError(f"g[{q}] = {gq} must be finite, in (0, 1) and above the g "
+                                 "before it")
+        self.fixed_weights = fixed_point_weights(self.weights)
+        if self.temperature.ndim != 1 or self.pressure.ndim != 1:
+            raise ValueError("temperatures and pressures must be 1-D")
+        self.n_bins, self.n_g = self.wl_bins.size - 1, self.g.size
+        self.shape = (self.pressure.size, self.temperature.size, self.n_bins, self.n_g)
+        self.tables = {}
+        for name, t in tables.items():
+            if not isinstance(t, CrossSection):
+                t = N.f64(t)
+                if t.shape != self.shape:
+                    raise ValueError(f"table {name!r} has shape {t.shape}, not (n_p, n_T, n_bins, "
+                                     f"n_g) = {self.shape}")
+            self.tables[name] = t
+        self.wavelength = np.repeat((self.wl_bins[:-1] + self.wl_bins[1:]) / 2, self.n_g)
+        self.device = device
+        self.kernel_ms = None
+        self._handle = None
+
+    @property
+    def n_src(self):
+        return len(self.names)
+
+    @property
+    def resident_bytes(self):
+        """Bytes of the species' tables in HBM."""
+        return 8 * self.n_src * int(np.prod(self.shape))
+
+    def handle(self):
+        """frei_klib* on the library's device (created and filled once)."""
+        if self._handle is None:
+            lib, h = N.lib(), ctypes.c_void_p()
+            N.check(lib.frei_klib_create(
+                ctypes.byref(h), self.device, self.n_src, self.pressure.size,
+                self.temperature.size, self.n_bins, self.n_g, N.dptr(self.wl_bins), N.dptr(self.g),
+                N.dptr(self.weights), N.dptr(self.pressure), N.dptr(self.temperature)))
+            self._handle = h
+            for s, t in enumerate(self.tables.values()):
+                if isinstance(t, CrossSection):
+                    N.check(lib.frei_klib_set_kdist(h, s, t.handle(self.device)))
+                else:
+                    N.check(lib.frei_klib_set(h, s, N.dptr(t)))
+        return self._handle
+
+    def release(self):
+        if self._handle is not None:
+            N.lib().frei_klib_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+    def composition(self, x):
+        """``x`` — mass mixing ratios at the nodes, (n_src, n_T, n_p) or (n_comp, n_src, n_T,
+        n_p), broadcast as ``CrossSection.mix`` broadcasts its weights — checked (finite, >= 0)
+        and transposed to the C layout [n_comp][n_src][n_p][n_T] -> (array, batched)."""
+        x = np.asarray(x, dtype=float)
+        one = (self.n_src, self.temperature.size, self.pressure.size)
+        batched = x.ndim == 4
+        if x.ndim > 4:
+            raise ValueError(f"x has {x.ndim} axes: (n_src, n_T, n_p) or (n_comp, n_src, n_T, n_p)")
+        try:
+            x = np.broadcast_to(x, ((x.shape[0],) if batched else (1,)) + one)
+        except ValueError:
+            raise ValueError(f"x of shape {x.shape} does not broadcast to (n_src, n_T, n_p) = "
+                             f"{one}") from None
+        if x.shape[0] < 1:
+            raise ValueError("x holds no composition")
+        bad = np.argwhere(~(np.isfinite(x) & (x >= 0)))
+        if bad.size:
+            c, s, t, p = bad[0]
+            raise ValueError(f"x[{c}][{s}][{t}][{p}] = {x[c, s, t, p]} (composition, species "
+                             f"{self.names[s]!r}, T node, p node) must be finite and >= 0")
+        return N.f64(x.transpose(0, 1, 3, 2)), batched
+
+    def mix(self, x, form=0, out=True):
+        """The mixture's k-table(s) on the host: (n_p, n_T, n_bins, n_g), or (n_comp, ...) for a
+        batch of compositions (``out=False``: they stay on the device, for timing, and None is
+        returned).  ``form``: 0 automatic (the wave form for n_g <= 2, the block form above),
+        1 the wave form (n_g <= 8), 2 the block form; the same bits.
+        ``kernel_ms`` receives the HIP-event time of the kernel."""
+        xc, batched = self.composition(x)
+        res = np.empty((xc.shape[0],) + self.shape) if out else None
+        ms = ctypes.c_double(0.0)
+        N.check(N.lib().frei_klib_mix(self.handle(), xc.shape[0], N.dptr(xc), N.dptr(res),
+                                      int(form), ctypes.byref(ms)))
+        self.kernel_ms = ms.value
+        if res is None or batched:
+            return res
+        return res[0]
+
+    def table(self, x):
+        """One composition's mixture as the table an Engine takes (no host round trip)."""
+        return MixedKTable(self, x)
+
+
+class MixedKTable:
+    """One composition of a :class:`KLibrary` mixed by random overlap (K19): nodes ``pressure``
+    (bar) x ``temperature`` (K), columns as a :class:`KTable`'s.  The Engine has the device mix
+    it directly into HBM (frei_set_table_kmix); ``values`` materialises it on the host."""
+
+    dims = ("pressure", "temperature", "wavelength")
+
+    def __init__(self, library, x):
+        self.library = library
+        xc, batched = library.composition(x)
+        if batched:
+            raise ValueError("a MixedKTable holds one composition: x is (n_src, n_T, n_p)")
+        self.x = xc[0]                      # [n_src][n_p][n_T], the C layout
+        self.pressure = library.pressure
+        self.temperature = library.temperature
+        self.wavelength = library.wavelength
+        self.wl_bins, self.g = library.wl_bins, library.g
+        self.device = library.device
+        self._values = None
+
+    @property
+    def n_bins(self):
+        return self.library.n_bins
+
+    @property
+    def shape(self):
+        return (self.pressure.size, self.temperature.size, self.wavelength.size)
+
+    @property
+    def values(self):
+        """(pressure, temperature, n_bins * n_g) on the host."""
+        if self._values is None:
+            self._values = self.library.mix(self.x.transpose(0, 2, 1)).reshape(self.shape)
+        return self._values
 
 
 def bin_counts(wavelength, wl_bins):

@@ -23,7 +23,7 @@ SOURCES = ["csrc/frei_kernels.hip", "csrc/frei_runtime.hip", "csrc/frei_binning.
            "csrc/frei_stellar.hip", "csrc/frei_transit.hip", "csrc/frei_observe.hip",
            "csrc/frei_emergent.hip", "csrc/frei_crosscorr.hip", "csrc/frei_broaden.hip",
            "csrc/frei_stack.hip", "csrc/frei_interp.hip", "csrc/frei_phase.hip",
-           "csrc/frei_lines.hip", "csrc/frei_kdist.hip"]
+           "csrc/frei_lines.hip", "csrc/frei_kdist.hip", "csrc/frei_kmix.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-std=c++17"]
 LIB = os.path.join(HERE, "libfrei_hip.so")
 STAMP = LIB + ".stamp"

@@ -609,5 +609,19 @@ int kdist_into_table(frei_xsec* x, const double* wl_bins, int64_t n_bins, int n_
                      const double* g, int64_t col_lo, int64_t n_out, const double* T_t, int n_T,
                      const double* p_t, int n_p, const int64_t* row_off, double* d_tab,
                      int device);
+}  // namespace frei
+struct frei_klib;
+namespace frei {
+// K19 (frei_kmix.hip): the checks of one composition x[n_src][n_p][n_T] of a library against the
+// columns [col_lo, col_lo + n_out) and a context's device, all on the host, and the library's
+// nodes (bar, K); then the mixture's columns into table rows d_tab + row_off[kp * n_T + kt].
+struct KlibNodes {
+  const double *p, *T;
+  int n_p, n_T;
+};
+int klib_table_args(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_out, int device,
+                    KlibNodes* out);
+int kmix_into_table(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_out,
+                    const int64_t* row_off, double* d_tab);
 
 }  // namespace frei

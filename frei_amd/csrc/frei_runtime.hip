@@ -1806,6 +1806,19 @@ int frei_set_table_kdist(frei_ctx* c, int s, frei_xsec* x, const double* wl_bins
   return scan_nan(c, s);
 }
 
+int frei_set_table_kmix(frei_ctx* c, int s, frei_klib* lib, const double* x, int64_t col_lo) {
+  if (!c || !lib || !x) return fail("null argument");
+  KlibNodes nd{};
+  TRY(klib_table_args(lib, x, col_lo, c->nlam, c->device, &nd));
+  TRY(set_device(c));
+  std::vector<double> p_cgs(nd.n_p);
+  for (int k = 0; k < nd.n_p; ++k) p_cgs[k] = nd.p[k] * 1e6;  // bar -> dyn cm^-2
+  TRY(set_table_common(c, s, p_cgs.data(), nd.n_p, nd.T, nd.n_T));
+  const std::vector<int64_t> row_off = node_row_offsets(c, s, nd.T, nd.n_T, nd.n_p);
+  TRY(kmix_into_table(lib, x, col_lo, c->nlam, row_off.data(), c->sp[s].d_tab));
+  return scan_nan(c, s);
+}
+
 int frei_set_mmr(frei_ctx* c, const double* mmr) {
   if (!c || !mmr) return fail("null argument");
   const size_t n = (size_t)c->S * c->nL * c->n_atm;

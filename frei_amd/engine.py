@@ -13,7 +13,7 @@ import os
 import numpy as np
 
 from . import _native as N
-from .binning import BinnedTable, KTable
+from .binning import BinnedTable, KTable, MixedKTable
 from .chemistry import ChemistryTable, fixed_provider_mmr, provider_mmr
 from .chemistry import chemistry as mock_chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, UM
@@ -256,6 +256,15 @@ class Engine:
                 self._ctx, s, tab.xsec.handle(self.device), N.dptr(tab.wl_bins), tab.n_bins,
                 tab.g.size, N.dptr(tab.g), N.dptr(tab.temperature), tab.temperature.size,
                 N.dptr(tab.pressure), tab.pressure.size, self.lo))
+            return
+        if isinstance(tab, MixedKTable):
+            if tab.wavelength.size != self.lam_um.size:
+                raise ValueError("k-table columns (n_bins * n_g) must match the grid's columns")
+            if tab.device != self.device:
+                raise ValueError(f"the k-table library lives on device {tab.device}, the engine "
+                                 f"on device {self.device}")
+            N.check(lib.frei_set_table_kmix(self._ctx, s, tab.library.handle(), N.dptr(tab.x),
+                                            self.lo))
             return
         if isinstance(tab, SeparableTable):
             N.check(lib.frei_set_table_separable(

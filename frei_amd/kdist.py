@@ -11,18 +11,21 @@ such a column is an ordinary column to all of them.
 
 The approximation: species are premixed at the table's (T, p) nodes (``CrossSection.mix``), k is
 interpolated in (p, T) at fixed g, and the spectral order inside a bin is taken to be the same
-in every layer (the layers' k are perfectly correlated).
+in every layer (the layers' k are perfectly correlated).  With ``overlap="random"`` (K19) the
+species are mixed from their own k-tables instead, their lines taken as uncorrelated
+(:class:`~frei_amd.binning.KLibrary`); a new composition then re-mixes the small tables and
+neither re-reads nor re-sorts a native cross-section (``KGrid.set_mix``).
 """
 import numpy as np
 
-from .binning import CrossSection, KTable
+from .binning import CrossSection, KLibrary, KTable, MixedKTable, bin_counts
 from .constants import UM
 from .core import F_TOA, Grid, Spectrum
 from .emergent import gauss_angles
 from .engine import Engine
 from .units import value
 
-__all__ = ["KGrid", "KTable", "gauss_g"]
+__all__ = ["KGrid", "KTable", "KLibrary", "MixedKTable", "gauss_g"]
 
 
 def gauss_g(n, split=None):
@@ -72,9 +75,10 @@ class KGrid(Grid):
         self.n_bins, self.n_g = self.lam.size, self.g.size
         self.col_lam = np.repeat(self.lam, self.n_g)
         self.col_weights = np.outer(np.diff(wl_bins) * UM, self.weights).ravel()
+        self.klibrary = None
 
     def load_opacities(self, cross_sections=None, mix=None, mmr=None, temperatures=None,
-                       pressures=None, chemistry=None):
+                       pressures=None, chemistry=None, ktables=None, overlap="premix"):
         """Attach the k-tables of ``cross_sections`` ({name: CrossSection}).  One cross-section
         becomes a :class:`KTable` under its own name, with ``mmr`` (or ``chemistry``) as in
         Grid.load_opacities.  Several need ``mix`` — their mass mixing ratios at the sources' own
@@ -82,7 +86,23 @@ class KGrid(Grid):
         ratio 1: the mixture is sorted, not the species.  The table's nodes are ``pressures``
         (default: the grid's layers, each taking its nearest source node as in Grid) x
         ``temperatures`` (default: the cross-section's own nodes, so that k is interpolated in T
-        at fixed g).  A bin that holds no point of the cross-section's axis is refused."""
+        at fixed g).  A bin that holds no point of the cross-section's axis is refused.
+
+        ``overlap="random"`` (K19) mixes the species from their own k-tables by random overlap
+        with resort-and-rebin instead of premixing the native cross-sections: from
+        ``cross_sections`` (each sorted once into a :class:`KLibrary` slot) or from
+        ``ktables={name: array[n_p][n_T][n_bins][n_g]}`` on the nodes ``temperatures`` x
+        ``pressures`` (default: the grid's layers).  ``mix`` is required; the library is kept as
+        ``grid.klibrary`` and the one species ``"mix"`` has mixing ratio 1.  :meth:`set_mix`
+        then changes the composition."""
+        if overlap not in ("premix", "random"):
+            raise ValueError(f"overlap must be 'premix' or 'random', not {overlap!r}")
+        if overlap == "random":
+            return self._load_random(cross_sections, ktables, mix, mmr, temperatures, pressures,
+                                     chemistry)
+        if ktables is not None:
+            raise ValueError("ktables= holds no native cross-section to premix: pass "
+                             "overlap='random'")
         if not cross_sections:
             raise ValueError("KGrid.load_opacities needs cross_sections={name: CrossSection}")
         xs = dict(cross_sections)
@@ -113,6 +133,53 @@ class KGrid(Grid):
         self.opacities = tables
         self.mmr = mmr
         self.chemistry = chemistry
+        self._close_engine()
+        return self.opacities
+
+    def _load_random(self, cross_sections, ktables, mix, mmr, temperatures, pressures, chemistry):
+        if bool(cross_sections) == bool(ktables):
+            raise ValueError("overlap='random' needs either cross_sections={name: CrossSection} "
+                             "or ktables={name: array}")
+        if mix is None:
+            raise ValueError("overlap='random' needs mix=: the species' mass mixing ratios at "
+                             "the table nodes, (n_src, n_T, n_p)")
+        if mmr is not None or chemistry is not None:
+            raise ValueError("mix= already holds the mixing ratios: the species 'mix' has "
+                             "mixing ratio 1, pass neither mmr nor chemistry")
+        p = self.pressures if pressures is None else value(pressures, "bar")
+        if ktables:
+            if temperatures is None:
+                raise ValueError("ktables= needs temperatures=: the tables' T nodes")
+            tables = dict(ktables)
+        else:
+            tables = dict(cross_sections)
+            if temperatures is None:
+                temperatures = next(iter(tables.values())).temperature
+            for name, x in tables.items():
+                bad = np.nonzero(bin_counts(x.wavelength, self.wl_bins) == 0)[0]
+                if bad.size:
+                    shown = ", ".join(str(k) for k in bad[:8]) + (", ..." if bad.size > 8 else "")
+                    raise ValueError(f"cross-section {name!r} does not cover the grid: bins "
+                                     f"{shown} hold no point")
+        lib = KLibrary(tables, self.wl_bins, self.g, self.weights, temperatures, p, self.device)
+        table = lib.table(mix)
+        if self.klibrary is not None:
+            self.klibrary.release()
+        self.klibrary = lib
+        self.opacities = {"mix": table}
+        self.mmr = np.ones((1, self.pressures.size))
+        self.chemistry = None
+        self._close_engine()
+        return self.opacities
+
+    def set_mix(self, mix):
+        """A new composition of the kept library (``load_opacities(..., overlap="random")``): the
+        species' k-tables are re-mixed on the device when the engine is next built; no native
+        cross-section is read or sorted again.  Closes the engine."""
+        if self.klibrary is None:
+            raise ValueError("set_mix needs the library load_opacities(..., overlap='random') "
+                             "keeps")
+        self.opacities = {"mix": self.klibrary.table(mix)}
         self._close_engine()
         return self.opacities
 

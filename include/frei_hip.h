@@ -578,6 +578,68 @@ int frei_set_table_kdist(frei_ctx* ctx, int s, frei_xsec* x, const double* wl_bi
                          const double* p_nodes, int n_p, int64_t col_lo);
 
 /*
+ * K19: a mixture's k-table from the species' k-tables by random overlap with resort-and-rebin
+ * (no reference counterpart; the method of Lacis & Oinas 1991 as every correlated-k code uses it).
+ *
+ * A frei_klib holds n_src k-tables K_s[n_p][n_T][n_bins][n_g] (float64) resident on one device.
+ * All share the nodes p_nodes[n_p] (bar) x T_nodes[n_T] (K), the bins wl_bins[n_bins + 1] (µm,
+ * strictly ascending) and one quadrature: g[n_g] strictly ascending in (0, 1), w[n_g] finite and
+ * positive, 1 <= n_g <= 64.
+ *
+ * Fixed-point weights.  W_q = llrint(w_q 2^30) in uint64, on the host; every W_q >= 1 and
+ * Wt = sum W_q <= 2^31, anything else is an argument error naming q.  The pair weights W_i W_j
+ * and their prefix sums stay below 2^62 in uint64: they are exact, so the result cannot depend
+ * on the order of the scan.  The interval of g-point q is [E_q, E_{q+1}) with
+ * E_q = Wt sum_{q' < q} W_q', in units of Wt^2.
+ *
+ * Mixing.  A composition is x[n_src][n_p][n_T], finite and >= 0: the mass mixing ratios at the
+ * table's nodes.  Per (composition, node, bin) start from a[q] = x_0 K_0[q]; then for
+ * s = 1 .. n_src - 1, in this order:
+ *   1. b[r] = x_s K_s[r].  Pair e = q n_g + r has the value v_e = a[q] + b[r] (the products
+ *      rounded, then the sum, unfused) and the weight u_e = W_q W_r.
+ *   2. The pairs are ordered by (v, e) ascending; v is compared as K18 compares: -0 as +0, every
+ *      NaN the canonical quiet NaN and last.  Ties go to the smaller e, so the order is total
+ *      whatever network sorts it.  Neither a nor b is assumed monotone.
+ *   3. C_e is the exact exclusive prefix sum of u in that order: pair e covers [C_e, C_e + u_e).
+ *   4. Per q, over the pairs that overlap q's interval, in sorted order: acc = +0.0, then
+ *      acc = acc + double(ov_e) log(v_e), ov_e the exact integer overlap (> 0);
+ *      a'[q] = exp(acc / double(W_q Wt)) — the weight-averaged geometric mean of k over the
+ *      interval.  log(0) = -inf gives 0; a negative or NaN value gives NaN in exactly the
+ *      intervals it overlaps.
+ *   5. a = a'.
+ * The result is out[n_p][n_T][n_bins][n_g] = a; with n_src = 1 it is x_0 K_0, with no log or exp.
+ *
+ * frei_klib_set copies a host table into slot s; frei_klib_set_kdist writes K18's k-distribution
+ * of a resident cross-section (frei_xsec_kdist at the library's nodes, bins and g) straight into
+ * slot s.  frei_klib_mix mixes n_comp compositions x[n_comp][n_src][n_p][n_T] into
+ * out[n_comp][n_p][n_T][n_bins][n_g] on the host (NULL: leave the result on the device, for
+ * timing).  form: 0 automatic (the wave form for n_g <= 2, the block form above, as measured),
+ * 1 the wave form (n_g <= 8 only: one pair per lane), 2 the block form; both give the same bits
+ * (frei_kmix.hip).  With form = 0, FREI_KMIX_FORM = auto, wave or block selects one
+ * for diagnostics.  *kernel_ms (may be NULL)
+ * receives the HIP-event time of the kernel.
+ *
+ * Every argument error is found on the host before any device call and names the first offender:
+ * a null pointer, a size below 1, n_g > 64, g not ascending in (0, 1), a bad weight, a slot out of
+ * range or not set, an x that is not finite or is negative, a device mismatch.
+ */
+typedef struct frei_klib frei_klib;
+int frei_klib_create(frei_klib** out, int device, int n_src, int n_p, int n_T, int64_t n_bins,
+                     int n_g, const double* wl_bins, const double* g, const double* w,
+                     const double* p_nodes, const double* T_nodes);
+int frei_klib_destroy(frei_klib* lib);
+int frei_klib_set(frei_klib* lib, int s, const double* k);
+int frei_klib_set_kdist(frei_klib* lib, int s, frei_xsec* x);
+int frei_klib_mix(frei_klib* lib, int n_comp, const double* x, double* out, int form,
+                  double* kernel_ms);
+/*
+ * One composition's mixture (x[n_src][n_p][n_T]) written straight into species s of a context,
+ * as frei_set_table_kdist writes a k-distribution: the context's n_lam columns are
+ * [col_lo, col_lo + n_lam) of the library's n_bins * n_g; the table gets the library's nodes.
+ */
+int frei_set_table_kmix(frei_ctx* ctx, int s, frei_klib* lib, const double* x, int64_t col_lo);
+
+/*
  * Stellar spectrum binning (phoenix.py:13-17, 43-52).  A frei_sspec is a library of model
  * spectra on one shared wavelength axis: flux[n_spec][n_hi] float64 resident in HBM on
  * wl_hi[n_hi] (um, strictly ascending).
