@@ -6,7 +6,7 @@ species-summed opacity assembly, radiative-equilibrium T-P loop): the public nam
 (``frei_amd/csrc``) behind the C ABI of ``include/frei_hip.h``.
 """
 from .batch import BatchEngine, BatchRecord, BatchResult, batched_emission_spectra
-from .binning import (BinnedTable, CrossSection, KLibrary, KTable, MixedKTable,
+from .binning import (BinnedTable, CrossSection, KLibrary, KTable, MixedKTable, MixedKTables,
                       open_cross_section)
 from .chemistry import ChemistryTable, chemistry, iso_to_mass, iso_to_species
 from .core import (B_star, F_TOA, Grid, Planet, Spectrum, contribution_function,
@@ -15,7 +15,7 @@ from .core import (B_star, F_TOA, Grid, Planet, Spectrum, contribution_function,
 from .crosscorr import CrossCorrelation, CrossCorrelator, kp_vsys_map
 from .broaden import BroadenedSpectra, Broadening, BroadeningKernel
 from .emergent import gauss_angles
-from .kdist import KGrid, gauss_g
+from .kdist import KBatchResult, KGrid, batched_k_spectra, gauss_g
 from .lines import LineList
 from .stack import OrbitStack
 from .modelgrid import InterpolatedSpectra, ModelGrid
@@ -41,4 +41,5 @@ __all__ = ["Planet", "Grid", "Spectrum", "effective_temperature", "wavelength_gr
            "StellarSpectra", "binned_stellar_spectrum", "get_binned_phoenix_spectrum",
            "level_radii", "Instrument", "gauss_angles", "CrossCorrelator", "CrossCorrelation",
            "kp_vsys_map", "OrbitStack", "ModelGrid", "InterpolatedSpectra", "PhaseCurve",
-           "PhaseSpectra", "lonlat_cells", "LineList", "KTable", "KGrid", "gauss_g"]
+           "PhaseSpectra", "lonlat_cells", "LineList", "KTable", "KGrid", "gauss_g", "KLibrary",
+           "MixedKTable", "MixedKTables", "batched_k_spectra", "KBatchResult"]

@@ -124,6 +124,9 @@ SIGNATURES = {
     "frei_klib_set_kdist": (ctypes.c_int, [_vp, ctypes.c_int, _vp]),
     "frei_klib_mix": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_int, _dp]),
     "frei_set_table_kmix": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _dp, _i64]),
+    "frei_set_table_kmix_batch": (ctypes.c_int, [_vp, _vp, _dp, _i64]),
+    "frei_kmix_batch_update": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp]),
+    "frei_get_table_batch": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
     "frei_sspec_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, _dp, ctypes.c_int,
                                          _i64, _dp]),
     "frei_sspec_bin": (ctypes.c_int, [_vp, _dp, _i64, ctypes.c_int, _dp,

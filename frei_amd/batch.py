@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
+from .binning import MixedKTables
 from .chemistry import ChemistryTable, chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, SIGMA_SB, UM
 from .emergent import emergent_call, pick
@@ -64,6 +65,41 @@ def stack_chemistry(tables, names):
     return N.f64(np.array([t.array(names) for t in tables]))
 
 
+def check_kmix(opacities, mmr, n_atm, n_lam, n_layers, device):
+    """The :class:`~frei_amd.binning.MixedKTables` of a k-mix batch (K20), or None when
+    ``opacities`` holds none; every misuse is a ValueError before any device call."""
+    mixed = [k for k, t in opacities.items() if isinstance(t, MixedKTables)]
+    if not mixed:
+        return None
+    if len(opacities) != 1:
+        others = [k for k in opacities if k not in mixed]
+        raise ValueError(f"a k-mix batch has the one species {mixed[0]!r}: the k(g) of several "
+                         f"species do not add, so {others or mixed[1:]} cannot stand beside it "
+                         "(put every species into the KLibrary)")
+    tabs = opacities[mixed[0]]
+    if tabs.n_comp != n_atm:
+        raise ValueError(f"{tabs.n_comp} compositions for n_atm = {n_atm} atmospheres")
+    if tabs.wavelength.size != n_lam:
+        raise ValueError("k-table columns (n_bins * n_g) must match the grid's columns")
+    if tabs.device != device:
+        raise ValueError(f"the k-table library lives on device {tabs.device}, the engine on "
+                         f"device {device}")
+    if mmr is not None:
+        if isinstance(mmr, (ChemistryTable, list, tuple)) and chemistry_tables(mmr, n_atm):
+            raise ValueError("a k-mix batch takes no chemistry tables: the compositions hold "
+                             "the mixing ratios")
+        m = np.asarray(mmr, dtype=float)
+        try:
+            np.broadcast_to(m, (n_atm, 1, n_layers))
+        except ValueError:
+            raise ValueError(f"mmr of shape {m.shape} does not broadcast to (n_atm, 1, "
+                             "n_layers)") from None
+        if not np.all(m == 1.0):
+            raise ValueError("mmr of a k-mix batch must be None or all ones: the compositions "
+                             "hold the mixing ratios")
+    return tabs
+
+
 class BatchEngine:
     """``n_atm`` atmospheres on ``device``: ``g`` [n_atm] (cm s^-2), ``mmr``
     [n_atm][n_species][n_layers], ``F_toa`` [n_lam] shared or [n_atm][n_lam] per atmosphere;
@@ -79,15 +115,34 @@ class BatchEngine:
     (``FREI_ATM_TILE``), so order such a batch by temperature.
 
     ``quad_weights`` (cm, one per column) replaces the trapezoid weights of the bolometric sums, as
-    in :class:`~frei_amd.engine.Engine` (a k-distribution's columns, ``KGrid.col_weights``)."""
+    in :class:`~frei_amd.engine.Engine` (a k-distribution's columns, ``KGrid.col_weights``).
+
+    A k-mix batch (K20): ``opacities = {"mix": MixedKTables}`` (``KLibrary.tables(x)``, one
+    composition per atmosphere) and nothing beside it; ``mmr`` is None or all ones.  The k(g) of
+    several species do not add, so each atmosphere's table is its own random-overlap mixture,
+    mixed on the device into the per-atmosphere tables the sweeps read
+    (frei_set_table_kmix_batch).  :meth:`set_mix` re-mixes all or some atmospheres in place and
+    :meth:`table` reads one atmosphere's table back.
+
+    ``k_weights`` (the quadrature weights w_q of a k-distribution whose columns ``b * n_g + q``
+    the engine runs on, ``KGrid.weights``) makes :meth:`post` finish on the bins: the Milne
+    pressure of bin b is ``sum_q w_q p_milne[b n_g + q]`` and the Milne mean weights the bins by
+    ``lam_b F_b`` of the collapsed spectrum (``frei_amd.core.milne_on_columns``)."""
 
     def __init__(self, lam_um, p_bar, opacities, g, mmr=None, m_bar=M_BAR_DEFAULT, F_toa=None,
-                 device=0, quad_weights=None):
+                 device=0, quad_weights=None, k_weights=None):
         lib = N.lib()
         self.lam_um = np.asarray(value(lam_um, "um"), dtype=float)
         self.p_bar = np.asarray(value(p_bar, "bar"), dtype=float)
         self.g = N.f64(np.atleast_1d(np.asarray(g, dtype=float)))
         self.n_atm = self.g.size
+        self.k_weights = None if k_weights is None else N.f64(np.atleast_1d(k_weights))
+        if self.k_weights is not None and (self.k_weights.ndim != 1 or
+                                           self.lam_um.size % self.k_weights.size):
+            raise ValueError(f"{self.lam_um.size} columns are no whole number of bins of "
+                             f"{self.k_weights.size} quadrature points")
+        self.kmix = check_kmix(opacities, mmr, self.n_atm, self.lam_um.size, self.p_bar.size,
+                               device)
         self.m_bar = scalar(m_bar, "g")
         self.names = list(opacities)
         self.n_layers = self.p_bar.size
@@ -116,11 +171,21 @@ class BatchEngine:
                 N.check(lib.frei_set_ftoa_batch(ctx, N.dptr(ft_atm)))
         self.lo = 0  # the whole wavelength grid
         # tables: the single-atmosphere engine's upload paths (shared by every atmosphere)
-        for s, name in enumerate(self.names):
-            Engine._set_table(self, s, opacities[name], slice(0, self.n_lam))
+        try:
+            if self.kmix is not None:   # one mixed table per atmosphere (K20)
+                N.check(lib.frei_set_table_kmix_batch(ctx, self.kmix.library.handle(),
+                                                      N.dptr(self.kmix.x), self.lo))
+            else:
+                for s, name in enumerate(self.names):
+                    Engine._set_table(self, s, opacities[name], slice(0, self.n_lam))
+        except BaseException:
+            self.close()
+            raise
         try:
             chem = chemistry_tables(mmr, self.n_atm)
-            if mmr is None or chem is not None:
+            if self.kmix is not None:
+                mmr = np.ones((1, self.n_layers))
+            elif mmr is None or chem is not None:
                 T0 = np.full(self.n_layers, 1000.0)
                 mm = chemistry(T0, self.p_bar, self.names, m_bar=self.m_bar)
                 mmr = np.array([mm[nm] for nm in self.names])
@@ -157,6 +222,43 @@ class BatchEngine:
             t0.pressure.size))
         self.chemistry = (tables, atm)
 
+    def set_mix(self, x, atm=None):
+        """New compositions of a k-mix batch, re-mixed in place on the device
+        (frei_kmix_batch_update; no new context, no metadata rebuild): ``x`` (n, n_src, n_T,
+        n_p) for the atmospheres ``atm`` (indices, in any order; default all ``n_atm``).  The
+        other atmospheres' tables keep their bits."""
+        if self.kmix is None:
+            raise ValueError("set_mix needs a k-mix batch: BatchEngine(..., {'mix': "
+                             "KLibrary.tables(x)}, ...)")
+        atm = np.arange(self.n_atm) if atm is None else np.atleast_1d(np.asarray(atm, dtype=int))
+        new = MixedKTables(self.kmix.library, x)
+        if atm.ndim != 1 or new.n_comp != atm.size:
+            raise ValueError(f"{new.n_comp} compositions for {atm.size} atmospheres")
+        bad = atm[(atm < 0) | (atm >= self.n_atm)]
+        if bad.size:
+            raise ValueError(f"atmosphere {bad[0]} lies outside [0, n_atm = {self.n_atm})")
+        lib = N.lib()
+        k = 0
+        while k < atm.size:            # one call per run of consecutive atmospheres
+            e = k + 1
+            while e < atm.size and atm[e] == atm[e - 1] + 1:
+                e += 1
+            N.check(lib.frei_kmix_batch_update(self._ctx, int(atm[k]), e - k,
+                                               N.dptr(N.f64(new.x[k:e]))))
+            self.kmix.x[atm[k:e]] = new.x[k:e]
+            k = e
+
+    def table(self, m):
+        """Atmosphere ``m``'s table of a k-mix batch as the sweeps read it, (n_p, n_T, n_lam) on
+        the library's nodes in their own order (frei_get_table_batch)."""
+        if self.kmix is None:
+            raise ValueError("table needs a k-mix batch: BatchEngine(..., {'mix': "
+                             "KLibrary.tables(x)}, ...)")
+        nd = self.kmix
+        out = np.empty((nd.pressure.size, nd.temperature.size, self.n_lam))
+        N.check(N.lib().frei_get_table_batch(self._ctx, int(m), N.dptr(out)))
+        return out
+
     def close(self):
         if getattr(self, "_ctx", None):
             N.lib().frei_ctx_destroy(self._ctx)
@@ -180,6 +282,7 @@ class BatchEngine:
         n_iter = (ctypes.c_int * self.n_atm)()
         T_final = np.empty((self.n_atm, self.n_layers))
         spectra = np.empty((self.n_atm, self.n_lam))
+        self._last_spectra = spectra
         if not (want_hist or keep_dtaus):
             N.check(N.lib().frei_run_batch(self._ctx, N.dptr(T), int(n_timesteps),
                                            int(n_zero_crossings), float(convergence_dT),
@@ -241,7 +344,7 @@ class BatchEngine:
             ratio = N.f64(p / ((1 - k) * p))
             nu = N.f64(1.0 / (self.lam_um * UM))
             cf = np.empty((A, nL, n))
-        pm = np.empty((A, n)) if want_p_milne else None
+        pm = np.empty((A, n)) if want_p_milne or self.k_weights is not None else None
         sums = np.empty((A, 3))
         N.check(N.lib().frei_post_batch(self._ctx, N.dptr(d), N.dptr(sp), N.dptr(Th),
                                         N.dptr(N.f64(p)), N.dptr(lam_cm), N.dptr(nu),
@@ -249,9 +352,22 @@ class BatchEngine:
                                         N.dptr(cf)))
         if Th is None:
             Th = self.get_temperatures()
-        T_milne = np.array([np.interp(sums[m, 0] / sums[m, 1], p[::-1], Th[m][::-1])
-                            for m in range(A)])
-        T_planck = (sums[:, 2] / SIGMA_SB) ** 0.25
+        if self.k_weights is not None:   # k-columns: the host finishes on the bins
+            from .core import collapse_columns, milne_on_columns, planck_temperature
+            if sp is None:
+                sp = getattr(self, "_last_spectra", None)
+            if sp is None:
+                raise ValueError("post on k-columns needs spectra= or a run before it")
+            w = self.k_weights
+            lam_b = self.lam_um[::w.size]
+            flux = collapse_columns(sp, w)
+            T_milne = np.array([milne_on_columns(pm[m], flux[m], lam_b, w, p, Th[m])
+                                for m in range(A)])
+            T_planck = np.array([planck_temperature(lam_b, flux[m]) for m in range(A)])
+        else:
+            T_milne = np.array([np.interp(sums[m, 0] / sums[m, 1], p[::-1], Th[m][::-1])
+                                for m in range(A)])
+            T_planck = (sums[:, 2] / SIGMA_SB) ** 0.25
         T_eff = np.array([float(np.mean([T_milne[m], T_planck[m]])) for m in range(A)])
         out = dict(T_milne=T_milne, T_planck=T_planck, T_eff=T_eff, sums=sums)
         if want_p_milne:
@@ -381,20 +497,23 @@ class BatchResult(list):
         area = eng.transit(radii, 1.0)
         return np.array([area[m] / (Rs[m] * Rs[m]) for m in range(A)])
 
+    def final_temperatures(self):
+        """[n_atm][n_layers]: each record's ``final_T``, K."""
+        return np.array([np.asarray(value(r.final_T, "K"), dtype=float) for r in self])
+
     def emergent(self, mu=None, weights=None, want_intensity=False):
         """Every atmosphere's ray-traced emergent flux [n_atm][n_lam] from each record's
         ``final_T`` and the dtaus the run left on the device, in one launch
         (BatchEngine.emergent: angles, weights and the return as there)."""
-        T = np.array([np.asarray(value(r.final_T, "K"), dtype=float) for r in self])
-        return self.engine.emergent(T, mu=mu, weights=weights, want_intensity=want_intensity)
+        return self.engine.emergent(self.final_temperatures(), mu=mu, weights=weights,
+                                    want_intensity=want_intensity)
 
     def phase_curve(self, pc, keep=False):
         """The phase spectra [n_phase][n_lam] of ``pc``
         (:class:`~frei_amd.phasecurve.PhaseCurve`, K16) from each record's ``final_T`` and the
         dtaus the run left on the device (BatchEngine.phase_curve): atmosphere ``m`` of the run
         is row ``m`` of ``pc.select``."""
-        T = np.array([np.asarray(value(r.final_T, "K"), dtype=float) for r in self])
-        return self.engine.phase_curve(pc, T, keep=keep)
+        return self.engine.phase_curve(pc, self.final_temperatures(), keep=keep)
 
     def observe(self, instrument, kind="eclipse", depth=None, weighting=None, data=None,
                 sigma=None, R_p=None, R_star=None, broadening=None):
@@ -510,8 +629,7 @@ def batched_emission_spectra(grids, n_timesteps=1, n_zero_crossings=2, convergen
     if any(hasattr(gr, "col_weights") for gr in grids):
         raise NotImplementedError(
             "batched_emission_spectra given KGrids: it would sum the columns of a k-distribution "
-            "with trapezoid weights; build BatchEngine(col_lam, ..., quad_weights=col_weights) "
-            "directly")
+            "with trapezoid weights, not quad_weights=col_weights; use batched_k_spectra")
     g0 = grids[0]
     for gr in grids[1:]:
         if not (np.array_equal(gr.lam, g0.lam) and np.array_equal(gr.pressures, g0.pressures)):

@@ -25,7 +25,8 @@ from . import _native as N
 from .chemistry import iso_to_species
 from .units import value
 
-__all__ = ["CrossSection", "BinnedTable", "KTable", "KLibrary", "MixedKTable", "binned_opacity",
+__all__ = ["CrossSection", "BinnedTable", "KTable", "KLibrary", "MixedKTable", "MixedKTables",
+           "binned_opacity",
            "open_cross_section", "fixed_point_weights", "GROUPIES", "EXACT"]
 
 GROUPIES, EXACT = 0, 1
@@ -318,14 +319,14 @@ class KLibrary:
             raise ValueError("temperatures and pressures must be 1-D")
         self.n_bins, self.n_g = self.wl_bins.size - 1, self.g.size
         self.shape = (self.pressure.size, self.temperature.size, self.n_bins, self.n_g)
-        self.tables = {}
+        self.sources = {}     # {name: array or CrossSection} (tables(x) is the K20 method)
         for name, t in tables.items():
             if not isinstance(t, CrossSection):
                 t = N.f64(t)
                 if t.shape != self.shape:
                     raise ValueError(f"table {name!r} has shape {t.shape}, not (n_p, n_T, n_bins, "
                                      f"n_g) = {self.shape}")
-            self.tables[name] = t
+            self.sources[name] = t
         self.wavelength = np.repeat((self.wl_bins[:-1] + self.wl_bins[1:]) / 2, self.n_g)
         self.device = device
         self.kernel_ms = None
@@ -349,7 +350,7 @@ class KLibrary:
                 self.temperature.size, self.n_bins, self.n_g, N.dptr(self.wl_bins), N.dptr(self.g),
                 N.dptr(self.weights), N.dptr(self.pressure), N.dptr(self.temperature)))
             self._handle = h
-            for s, t in enumerate(self.tables.values()):
+            for s, t in enumerate(self.sources.values()):
                 if isinstance(t, CrossSection):
                     N.check(lib.frei_klib_set_kdist(h, s, t.handle(self.device)))
                 else:
@@ -409,6 +410,45 @@ class KLibrary:
     def table(self, x):
         """One composition's mixture as the table an Engine takes (no host round trip)."""
         return MixedKTable(self, x)
+
+    def tables(self, x):
+        """A batch of compositions (n_comp, n_src, n_T, n_p) as the per-atmosphere tables a
+        BatchEngine takes (K20; no host round trip)."""
+        return MixedKTables(self, x)
+
+
+class MixedKTables:
+    """``n_comp`` compositions of a :class:`KLibrary`, one per atmosphere of a batch (K20): the
+    batched counterpart of :class:`MixedKTable`.  A BatchEngine has the device mix each
+    atmosphere's table straight into HBM (frei_set_table_kmix_batch); ``x`` is kept in the C
+    layout [n_comp][n_src][n_p][n_T]."""
+
+    dims = ("pressure", "temperature", "wavelength")
+
+    def __init__(self, library, x):
+        self.library = library
+        x = np.asarray(x, dtype=float)
+        if x.ndim != 4:
+            raise ValueError(f"x of shape {x.shape} is not a batch of compositions: "
+                             "(n_comp, n_src, n_T, n_p)")
+        self.x, _ = library.composition(x)
+        self.pressure = library.pressure
+        self.temperature = library.temperature
+        self.wavelength = library.wavelength
+        self.wl_bins, self.g = library.wl_bins, library.g
+        self.device = library.device
+
+    @property
+    def n_comp(self):
+        return self.x.shape[0]
+
+    @property
+    def n_bins(self):
+        return self.library.n_bins
+
+    def __getitem__(self, m):
+        """Composition ``m`` as a :class:`MixedKTable`."""
+        return MixedKTable(self.library, self.x[m].transpose(0, 2, 1))
 
 
 class MixedKTable:

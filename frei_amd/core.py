@@ -280,7 +280,8 @@ def effective_temperature_milne(grid, spec, dtaus, final_temps):
     if hasattr(grid, "col_weights"):
         raise NotImplementedError(
             "effective_temperature_milne on a KGrid: the Milne mean weights wavelengths, not the "
-            "columns of a k-distribution (bin width x quadrature weight); not implemented yet")
+            "columns of a k-distribution (bin width x quadrature weight); use "
+            "KGrid.effective_temperature_milne, or batched_k_spectra(..., post=True) for a batch")
     lam = np.asarray(grid.lam)
     p = np.asarray(grid.pressures)
     eng, d = _post_engine(grid, dtaus)
@@ -299,12 +300,41 @@ def contribution_function(grid, dtaus, final_temps):
     return eng.contribution(np.asarray(grid.pressures), np.asarray(final_temps), d)
 
 
-def effective_temperature_planck(grid, spec):
-    """Stefan-Boltzmann inversion of the bolometric flux (core.py:408-414)."""
-    lam_cm = np.asarray(grid.lam) * UM
-    f = np.asarray(spec.flux)
+def planck_temperature(lam_um, flux):
+    """(trapezoid integral of ``flux`` over ``lam_um`` / sigma_SB)^(1/4), K."""
+    lam_cm = np.asarray(lam_um) * UM
+    f = np.asarray(flux)
     bol = np.sum(np.diff(lam_cm) * (f[1:] + f[:-1]) / 2.0)
     return (bol / SIGMA_SB) ** 0.25
+
+
+def effective_temperature_planck(grid, spec):
+    """Stefan-Boltzmann inversion of the bolometric flux (core.py:408-414)."""
+    return planck_temperature(grid.lam, spec.flux)
+
+
+def collapse_columns(x, weights):
+    """[..., n_bins * n_g] -> [..., n_bins]: the g-average ``sum_q w_q x[b n_g + q]`` of a
+    k-distribution's columns, q ascending, on the host."""
+    x, w = np.asarray(x), np.asarray(weights, dtype=float)
+    if x.shape[-1] % w.size:
+        raise ValueError(f"{x.shape[-1]} columns are no whole number of bins of {w.size} points")
+    x = x.reshape(x.shape[:-1] + (x.shape[-1] // w.size, w.size))
+    out = np.zeros(x.shape[:-1], dtype=np.result_type(x.dtype, float))
+    for q in range(w.size):
+        out = out + w[q] * x[..., q]
+    return out
+
+
+def milne_on_columns(p_milne, flux, lam_um, weights, pressures, final_temps):
+    """Milne's photosphere temperature on the columns of a k-distribution (K20):
+    ``p_b = sum_q w_q p_milne[b n_g + q]`` (q ascending, as :func:`collapse_columns` sums), then
+    the reference's formula on the bins (core.py:386-405): ``interp(average(p_b, weights =
+    lam_b F_b))`` with ``flux`` = F_b the collapsed spectrum on the bin centres ``lam_um``."""
+    p_b = collapse_columns(p_milne, weights)
+    lam_flux = np.asarray(flux) * (np.asarray(lam_um) * UM)
+    p = np.asarray(pressures)
+    return np.interp(np.average(p_b, weights=lam_flux), p[::-1], np.asarray(final_temps)[::-1])
 
 
 def effective_temperature(grid, spec, dtaus, final_temps):

@@ -617,11 +617,24 @@ namespace frei {
 // nodes (bar, K); then the mixture's columns into table rows d_tab + row_off[kp * n_T + kt].
 struct KlibNodes {
   const double *p, *T;
-  int n_p, n_T;
+  int n_p, n_T, n_src;
 };
 int klib_table_args(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_out, int device,
                     KlibNodes* out);
 int kmix_into_table(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_out,
                     const int64_t* row_off, double* d_tab);
+// K20: one row of a mix's row list — node `node` of composition `comp` goes to the row that
+// starts at element `dst` of the destination.  klib_batch_args checks n_comp compositions
+// x[n_comp][n_src][n_p][n_T] as klib_table_args checks one (`me` prefixes the message);
+// kmix_rows_into mixes the listed rows' columns [col_lo, col_lo + n_out) into d_out on the
+// stream st and returns when st has finished.
+struct KmixRow {
+  int32_t comp, node;
+  int64_t dst;
+};
+int klib_batch_args(const std::string& me, frei_klib* lib, int n_comp, const double* x,
+                    int64_t col_lo, int64_t n_out, int device, KlibNodes* out);
+int kmix_rows_into(frei_klib* lib, int n_comp, const double* x, int64_t col_lo, int64_t n_out,
+                   const KmixRow* rows, size_t n_rows, double* d_out, hipStream_t st);
 
 }  // namespace frei

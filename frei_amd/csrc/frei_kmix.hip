@@ -6,9 +6,10 @@
 // straight into a context.  No reference counterpart: every correlated-k code mixes this way
 // (Lacis & Oinas 1991; Amundsen et al. 2017, "random overlap with resorting and rebinning").
 //
-// One work item per (composition, node, bin); the running a[n_g] stays on chip over the species
-// loop.  Per fold the n_g^2 pair values v_e = a[q] + b[r] become 64-bit order-preserving keys
-// (-0 -> +0, every NaN the canonical quiet NaN, which sorts last), the pairs are sorted by
+// One work item per (listed row, bin), a row being one (composition, node) pair with its own
+// destination (K20: a batch of atmospheres lists only the pressure rows its layers sit on); the
+// running a[n_g] stays on chip over the species loop.  Per fold the n_g^2 pair values
+// v_e = a[q] + b[r] become 64-bit order-preserving keys (-0 -> +0, every NaN the canonical quiet NaN, which sorts last), the pairs are sorted by
 // (key, e), the fixed-point pair weights are scanned exactly in uint64, and lane q sums
 // double(overlap) * log(v) over the pairs that overlap its quadrature interval, in sorted order.
 // Two forms; the automatic choice is the wave form for n_g <= 2 and the block form above, as
@@ -66,13 +67,14 @@ struct KmixArgs {
   const double* x;       // [n_comp][n_src][n_nodes]
   const uint64_t* W;     // [n_g]
   const uint64_t* E;     // [n_g + 1]
-  const int64_t* dst;    // [n_comp * n_nodes] element offset of each (composition, node) row
+  const KmixRow* rows;   // [n_rows] the (composition, node) pairs to mix, each with the element
+                         // offset of its destination row in out
   double* out;
   int64_t col_lo, n_out; // the columns [col_lo, col_lo + n_out) of the n_bins * n_g are stored
   int64_t slot;          // n_nodes * n_bins * n_g: values of one table
   int n_src, n_nodes, n_bins, n_g;
   int bin_lo, nbl;       // the bins [bin_lo, bin_lo + nbl) are mixed
-  unsigned n_items;      // n_comp * n_nodes * nbl
+  unsigned n_items;      // n_rows * nbl
   unsigned first;        // the launch's first item (a launch is kept below 2^31 lanes)
 };
 
@@ -108,24 +110,27 @@ __device__ __forceinline__ uint64_t wave_scan(uint64_t v, int lane) {
   return v;
 }
 
-// Item w = (composition * n_nodes + node) * nbl + (bin - bin_lo).
+// Item w = listed row * nbl + (bin - bin_lo).
 struct Item {
-  int row, bin;
+  int bin;
+  int64_t dst;        // element offset of the row's column 0 in out
   const double* k0;   // K_0 of the item's (node, bin)
   const double* x0;   // x_0 of its (composition, node)
 };
 __device__ __forceinline__ Item item_of(const KmixArgs& a, unsigned w) {
   Item it;
-  it.row = (int)(w / (unsigned)a.nbl);
-  it.bin = a.bin_lo + (int)(w - (unsigned)it.row * (unsigned)a.nbl);
-  const int c = it.row / a.n_nodes, nd = it.row - c * a.n_nodes;
+  const unsigned row = w / (unsigned)a.nbl;
+  it.bin = a.bin_lo + (int)(w - row * (unsigned)a.nbl);
+  const KmixRow r = a.rows[row];
+  const int c = r.comp, nd = r.node;
+  it.dst = r.dst;
   it.k0 = a.k + ((int64_t)nd * a.n_bins + it.bin) * a.n_g;
   it.x0 = a.x + (int64_t)c * a.n_src * a.n_nodes + nd;
   return it;
 }
 __device__ __forceinline__ void store(const KmixArgs& a, const Item& it, int q, double v) {
   const int64_t c = (int64_t)it.bin * a.n_g + q - a.col_lo;
-  if (c >= 0 && c < a.n_out) a.out[a.dst[it.row] + c] = v;
+  if (c >= 0 && c < a.n_out) a.out[it.dst + c] = v;
 }
 
 // wave form: wave (blockIdx.x * 4 + wave of the block) is the item; n_g <= 8.
@@ -327,10 +332,20 @@ int check_mix(const std::string& me, const frei_klib* lib, int n_comp, const dou
   return 0;
 }
 
-// The mixture's columns [col_lo, col_lo + n_out) of n_comp compositions (already checked) into
-// d_out, row (composition, node) at dst[c * n_nodes + node].
+// Every (composition, node) row, row (c, node) at dst[c * n_nodes + node]: the full list.
+std::vector<KmixRow> all_rows(int n_comp, int n_nodes, const int64_t* dst) {
+  std::vector<KmixRow> rows((size_t)n_comp * n_nodes);
+  for (int c = 0; c < n_comp; ++c)
+    for (int nd = 0; nd < n_nodes; ++nd)
+      rows[(size_t)c * n_nodes + nd] = KmixRow{c, nd, dst[(size_t)c * n_nodes + nd]};
+  return rows;
+}
+
+// The mixture's columns [col_lo, col_lo + n_out) of the listed rows of n_comp compositions (already
+// checked) into d_out on the stream st; the call returns when the stream has finished.
 int mix_into(frei_klib* lib, int n_comp, const double* x, int64_t col_lo, int64_t n_out,
-             const std::vector<int64_t>& dst, double* d_out, int form, double* kernel_ms) {
+             const KmixRow* rows, size_t n_rows, double* d_out, int form, double* kernel_ms,
+             hipStream_t st) {
   const int n_nodes = lib->n_p * lib->n_T;
   KmixArgs a{};
   a.k = lib->d_k;
@@ -346,11 +361,11 @@ int mix_into(frei_klib* lib, int n_comp, const double* x, int64_t col_lo, int64_
   a.n_g = lib->n_g;
   a.bin_lo = (int)(col_lo / lib->n_g);
   a.nbl = (int)((col_lo + n_out - 1) / lib->n_g) - a.bin_lo + 1;
-  a.n_items = (unsigned)((int64_t)n_comp * n_nodes * a.nbl);
+  a.n_items = (unsigned)((int64_t)n_rows * a.nbl);
   const int P = block_P(lib->n_g);
-  DeviceCall call(lib->stream, "k-table mix");
+  DeviceCall call(st, "k-table mix");
   a.x = call.upload(x, (size_t)n_comp * lib->n_src * n_nodes);
-  a.dst = call.upload(dst.data(), dst.size());
+  a.rows = call.upload(rows, n_rows);
   if (call.ok() && form == kBlock && block_lds(P) > 64 * 1024 &&
       hipFuncSetAttribute(reinterpret_cast<const void*>(&kmix_block_kernel),
                           hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -364,9 +379,9 @@ int mix_into(frei_klib* lib, int n_comp, const double* x, int64_t col_lo, int64_
     for (a.first = 0; a.first < a.n_items; a.first += per) {
       const unsigned n = std::min(per, a.n_items - a.first);
       if (form == kWave)
-        kmix_wave_kernel<<<(n + 3u) / 4u, nt, 0, lib->stream>>>(a);
+        kmix_wave_kernel<<<(n + 3u) / 4u, nt, 0, st>>>(a);
       else
-        kmix_block_kernel<<<n, nt, block_lds(P), lib->stream>>>(a, P);
+        kmix_block_kernel<<<n, nt, block_lds(P), st>>>(a, P);
     }
   }
   call.end();
@@ -384,7 +399,7 @@ int klib_table_args(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_o
   if (lib->device != device)
     return set_error(me + "the library lives on device " + std::to_string(lib->device) +
                      ", the context on device " + std::to_string(device));
-  *out = KlibNodes{lib->p.data(), lib->T.data(), lib->n_p, lib->n_T};
+  *out = KlibNodes{lib->p.data(), lib->T.data(), lib->n_p, lib->n_T, lib->n_src};
   return 0;
 }
 
@@ -393,8 +408,28 @@ int kmix_into_table(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_o
   int form = kAuto;
   TRY(check_mix("frei_set_table_kmix: ", lib, 1, x, col_lo, n_out, &form));
   HIP_TRY(hipSetDevice(lib->device));
-  const std::vector<int64_t> dst(row_off, row_off + (size_t)lib->n_p * lib->n_T);
-  return mix_into(lib, 1, x, col_lo, n_out, dst, d_tab, form, nullptr);
+  const std::vector<KmixRow> rows = all_rows(1, lib->n_p * lib->n_T, row_off);
+  return mix_into(lib, 1, x, col_lo, n_out, rows.data(), rows.size(), d_tab, form, nullptr,
+                  lib->stream);
+}
+
+int klib_batch_args(const std::string& me, frei_klib* lib, int n_comp, const double* x,
+                    int64_t col_lo, int64_t n_out, int device, KlibNodes* out) {
+  int form = kAuto;
+  TRY(check_mix(me, lib, n_comp, x, col_lo, n_out, &form));
+  if (lib->device != device)
+    return set_error(me + "the library lives on device " + std::to_string(lib->device) +
+                     ", the context on device " + std::to_string(device));
+  if (out) *out = KlibNodes{lib->p.data(), lib->T.data(), lib->n_p, lib->n_T, lib->n_src};
+  return 0;
+}
+
+int kmix_rows_into(frei_klib* lib, int n_comp, const double* x, int64_t col_lo, int64_t n_out,
+                   const KmixRow* rows, size_t n_rows, double* d_out, hipStream_t st) {
+  int form = kAuto;
+  TRY(check_mix("frei_kmix_batch_update: ", lib, n_comp, x, col_lo, n_out, &form));
+  if (n_rows == 0) return 0;
+  return mix_into(lib, n_comp, x, col_lo, n_out, rows, n_rows, d_out, form, nullptr, st);
 }
 }  // namespace frei
 
@@ -543,7 +578,9 @@ int frei_klib_mix(frei_klib* lib, int n_comp, const double* x, double* out, int 
   }
   std::vector<int64_t> dst(rows);
   for (size_t r = 0; r < rows; ++r) dst[r] = (int64_t)r * n_col;
-  TRY(mix_into(lib, n_comp, x, 0, n_col, dst, lib->d_out, form, kernel_ms));
+  const std::vector<KmixRow> list = all_rows(n_comp, lib->n_p * lib->n_T, dst.data());
+  TRY(mix_into(lib, n_comp, x, 0, n_col, list.data(), list.size(), lib->d_out, form, kernel_ms,
+               lib->stream));
   if (out) HIP_TRY(hipMemcpy(out, lib->d_out, total * sizeof(double), hipMemcpyDeviceToHost));
   return 0;
 }

@@ -269,6 +269,17 @@ struct frei_ctx {
   // (0: not a chemistry batch)
   int atm_tile = -1;
   int tile = 0;
+  // K20, a k-mix batch (frei_set_table_kmix_batch): the k(g) of several species do not add, so
+  // atmosphere m's table in d_eff is the random-overlap mixture (K19) of its own composition
+  // kmix_x[m], written by the K19 kernels through a row list instead of K7's species sum.  Only
+  // the pressure rows some layer sits on (kmix_used) are mixed.  kmix_lib is the caller's and
+  // must outlive the context's use of it.
+  frei_klib* kmix_lib = nullptr;
+  std::vector<double> kmix_x;        // [n_atm][n_src][n_p][n_T]
+  int64_t kmix_col_lo = 0;
+  int kmix_nsrc = 0;
+  std::vector<int32_t> kmix_rank;    // [n_T] storage row (ascending T) of the library's node kt
+  std::vector<char> kmix_used;       // [n_p] a layer sits on the row (the last metadata build)
   // P2P exchange over xGMI (frei_comm_p2p_*): own mailbox (uncached device memory), the
   // mapped mailboxes of every rank (own included) and the per-sweep sequence number
   double* d_mbox = nullptr;
@@ -391,15 +402,57 @@ int atm_tile_width(const frei_ctx* c, bool shared_nodes) {
   return t;
 }
 
+// K20: the tables of the atmospheres [atm_lo, atm_lo + n) of a k-mix batch mixed into d_eff on
+// the context's stream, each (used pressure row, T node) a row of K19's list; then a NaN in any
+// of them fails the call and names the first atmosphere.  The rest of each table (the other
+// rows, the column padding, the tail) is zero since the metadata build and is not touched.
+int kmix_fill(frei_ctx* c, int atm_lo, int n) {
+  const Species& q0 = c->sp[0];
+  std::vector<KmixRow> rows;
+  for (int i = 0; i < n; ++i)
+    for (int kp = 0; kp < q0.n_p; ++kp)
+      for (int kt = 0; kt < q0.n_T && c->kmix_used[kp]; ++kt)
+        rows.push_back(KmixRow{i, kp * q0.n_T + kt,
+                               (int64_t)((size_t)(atm_lo + i) * c->eff_stride) +
+                                   ((int64_t)kp * q0.n_T + c->kmix_rank[kt]) * q0.stride});
+  const size_t per_x = (size_t)c->kmix_nsrc * q0.n_p * q0.n_T;
+  TRY(kmix_rows_into(c->kmix_lib, n, c->kmix_x.data() + (size_t)atm_lo * per_x, c->kmix_col_lo,
+                     c->nlam, rows.data(), rows.size(), c->d_eff, c->stream));
+  int* d_flag = nullptr;
+  TRY(dalloc(&d_flag, (size_t)n));
+  std::vector<int> flag((size_t)n, 0);
+  int rc = 0;
+  if (hipMemsetAsync(d_flag, 0, (size_t)n * sizeof(int), c->stream) != hipSuccess) rc = 1;
+  for (int i = 0; i < n && !rc; ++i)
+    launch_nan_scan(c->d_eff + (size_t)(atm_lo + i) * c->eff_stride,
+                    (int64_t)q0.n_p * q0.n_T * q0.stride, d_flag + i, c->stream);
+  if (!rc && (hipGetLastError() != hipSuccess ||
+              hipMemcpyAsync(flag.data(), d_flag, (size_t)n * sizeof(int), hipMemcpyDeviceToHost,
+                             c->stream) != hipSuccess ||
+              hipStreamSynchronize(c->stream) != hipSuccess))
+    rc = 1;
+  dfree(d_flag);
+  if (rc) return fail("the NaN scan of the mixed tables failed");
+  for (int i = 0; i < n; ++i)
+    if (flag[i])
+      return fail("the mixed table of atmosphere " + std::to_string(atm_lo + i) +
+                  " holds a NaN in a row a layer uses (a batched context needs tables without "
+                  "NaN)");
+  return 0;
+}
+
 template <typename Lap>
 int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   const int nL = c->nL, S = c->S;
   c->lazy_on = false;        // (decided below, with the contracted table)
   c->eff_complete = true;
   const bool batch = c->n_atm > 1;
+  // a k-mix batch (K20): species 0 carries the nodes (and composition 0's mixture, which a
+  // context of one atmosphere sweeps as it is); the per-atmosphere tables are mixed below
+  const bool kmix = batch && c->kmix_lib != nullptr;
   // (a T-dependent chemistry changes mmr every sweep: the species sum stays in the sweep)
   bool on = shared_fast && (S >= 2 || batch) && (c->eff_mode != 0 || batch) && !c->chem_on;
-  for (int s = 0; s < S && on; ++s) on = !c->sp[s].has_nan;
+  for (int s = 0; s < S && on && !kmix; ++s) on = !c->sp[s].has_nan;
   std::vector<int32_t> prow(nL, 0);
   if (on) {
     std::vector<int> owner((size_t)c->sp[0].n_p, -1);
@@ -460,7 +513,13 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
       }
       HIP_TRY(hipMemsetAsync(base + (size_t)q0.n_p * rowblk, 0, 64 * sizeof(double),
                              c->stream));
+      // (K19 writes the n_lam columns of a row: the padding up to the pitch is cleared here)
+      if (kmix && q0.stride > c->nlam)
+        HIP_TRY(hipMemset2DAsync(base + c->nlam, (size_t)q0.stride * sizeof(double), 0,
+                                 (size_t)(q0.stride - c->nlam) * sizeof(double),
+                                 (size_t)q0.n_p * q0.n_T, c->stream));
     }
+    if (kmix) c->kmix_used = used;
   }
   lap(3);
   if (!c->d_ones) {
@@ -497,7 +556,14 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   if (hipEventCreate(&k0) != hipSuccess || hipEventCreate(&k1) != hipSuccess)
     return fail("hipEventCreate failed");
   HIP_TRY(hipEventRecord(k0, c->stream));
-  if (batch && c->k7_mfma)  // K7: [n_atm x S] . [S x n_T*pitch] per layer on fp64 MFMA
+  if (kmix) {               // K20: K19's random-overlap mixture per atmosphere, not a species sum
+    const int rc = kmix_fill(c, 0, c->n_atm);
+    if (rc) {
+      (void)hipEventDestroy(k0);
+      (void)hipEventDestroy(k1);
+      return rc;
+    }
+  } else if (batch && c->k7_mfma)  // K7: [n_atm x S] . [S x n_T*pitch] per layer on fp64 MFMA
     launch_contract_batch(tabs, S, c->d_mmr, c->d_prow, nL, q0.n_T, q0.stride, c->n_atm,
                           (int64_t)per, c->d_eff, c->stream);
   else if (batch)           // K7 on the VALU, K3's species order
@@ -1693,6 +1759,7 @@ static int set_table_common(frei_ctx* c, int s, const double* p_nodes, int n_p,
   const std::vector<int32_t> perm = t_order(T_nodes, n_T);
   q.T_nodes.resize(n_T);
   for (int t = 0; t < n_T; ++t) q.T_nodes[t] = T_nodes[perm[t]];  // stored ascending
+  c->kmix_lib = nullptr;   // a new table ends a k-mix batch (frei_set_table_kmix_batch sets it after)
   c->meta_dirty = true;
   return 0;
 }
@@ -1819,8 +1886,107 @@ int frei_set_table_kmix(frei_ctx* c, int s, frei_klib* lib, const double* x, int
   return scan_nan(c, s);
 }
 
+int frei_set_table_kmix_batch(frei_ctx* c, frei_klib* lib, const double* x, int64_t col_lo) {
+  const std::string me = "frei_set_table_kmix_batch: ";
+  if (!c || !lib || !x) return fail(me + "null argument");
+  if (!c->batch_api) return fail(me + "needs a context from frei_ctx_create_batch");
+  if (c->S != 1)
+    return fail(me + "needs n_species = 1 (the mixture is the one species), not n_species = " +
+                std::to_string(c->S));
+  if (!c->grid_set) return fail(me + "frei_set_grid must be called first");
+  if (c->chem_on)
+    return fail(me + "the context holds chemistry tables (frei_set_chemistry_batch); a k-mix "
+                     "batch's compositions hold the mixing ratios");
+  KlibNodes nd{};
+  TRY(klib_batch_args(me, lib, c->n_atm, x, col_lo, c->nlam, c->device, &nd));
+  TRY(set_device(c));
+  std::vector<double> p_cgs(nd.n_p);
+  for (int k = 0; k < nd.n_p; ++k) p_cgs[k] = nd.p[k] * 1e6;  // bar -> dyn cm^-2
+  TRY(set_table_common(c, 0, p_cgs.data(), nd.n_p, nd.T, nd.n_T));
+  const std::vector<int64_t> row_off = node_row_offsets(c, 0, nd.T, nd.n_T, nd.n_p);
+  TRY(kmix_into_table(lib, x, col_lo, c->nlam, row_off.data(), c->sp[0].d_tab));
+  TRY(scan_nan(c, 0));
+  const std::vector<int32_t> perm = t_order(nd.T, nd.n_T);
+  c->kmix_rank.assign(nd.n_T, 0);
+  for (int t = 0; t < nd.n_T; ++t) c->kmix_rank[perm[t]] = t;
+  c->kmix_x.assign(x, x + (size_t)c->n_atm * nd.n_src * nd.n_p * nd.n_T);
+  c->kmix_col_lo = col_lo;
+  c->kmix_nsrc = nd.n_src;
+  c->kmix_lib = lib;
+  c->mmr.assign((size_t)c->nL * c->n_atm, 1.0);
+  c->meta_dirty = true;
+  return build_meta(c);   // the per-atmosphere tables are mixed here
+}
+
+int frei_kmix_batch_update(frei_ctx* c, int atm_lo, int n, const double* x) {
+  const std::string me = "frei_kmix_batch_update: ";
+  if (!c || !x) return fail(me + "null argument");
+  if (!c->kmix_lib)
+    return fail(me + "the context holds no k-mix batch (frei_set_table_kmix_batch)");
+  if (atm_lo < 0 || n < 1 || (int64_t)atm_lo + n > c->n_atm)
+    return fail(me + "atmospheres [" + std::to_string(atm_lo) + ", " +
+                std::to_string((int64_t)atm_lo + n) + ") lie outside [0, n_atm = " +
+                std::to_string(c->n_atm) + ")");
+  TRY(klib_batch_args(me, c->kmix_lib, n, x, c->kmix_col_lo, c->nlam, c->device, nullptr));
+  TRY(set_device(c));
+  const Species& q0 = c->sp[0];
+  const size_t per_x = (size_t)c->kmix_nsrc * q0.n_p * q0.n_T;
+  std::copy(x, x + (size_t)n * per_x, c->kmix_x.begin() + (size_t)atm_lo * per_x);
+  if (c->n_atm == 1) {   // the one atmosphere sweeps species 0's table: re-mixed in place
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<int64_t> row_off((size_t)q0.n_p * q0.n_T);
+    for (int kp = 0; kp < q0.n_p; ++kp)
+      for (int kt = 0; kt < q0.n_T; ++kt)
+        row_off[(size_t)kp * q0.n_T + kt] = ((int64_t)kp * q0.n_T + c->kmix_rank[kt]) * q0.stride;
+    TRY(kmix_into_table(c->kmix_lib, x, c->kmix_col_lo, c->nlam, row_off.data(), q0.d_tab));
+    const int had = q0.has_nan;
+    TRY(scan_nan(c, 0));
+    if (c->sp[0].has_nan != had) c->meta_dirty = true;   // the sweep's NaN skip changes
+    return 0;
+  }
+  if (c->meta_dirty) return 0;   // the next metadata build mixes every atmosphere
+  const int rc = kmix_fill(c, atm_lo, n);
+  if (rc) c->meta_dirty = true;   // no run on a table that holds a NaN
+  return rc;
+}
+
+int frei_get_table_batch(frei_ctx* c, int atm, double* out) {
+  const std::string me = "frei_get_table_batch: ";
+  if (!c || !out) return fail(me + "null argument");
+  if (!c->batch_api) return fail(me + "needs a context from frei_ctx_create_batch");
+  if (atm < 0 || atm >= c->n_atm)
+    return fail(me + "atmosphere " + std::to_string(atm) + " lies outside [0, n_atm = " +
+                std::to_string(c->n_atm) + ")");
+  TRY(set_device(c));
+  TRY(build_meta(c));
+  if (!c->eff && c->S != 1)
+    return fail(me + "the sweeps of this context sum the species themselves: it has no "
+                     "per-atmosphere table");
+  const Species& q0 = c->sp[0];
+  const double* src = c->eff ? c->d_eff + (size_t)atm * c->eff_stride : q0.d_tab;
+  const size_t rows = (size_t)q0.n_p * q0.n_T, n = (size_t)c->nlam;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const bool perm = c->kmix_lib != nullptr;
+  std::vector<double> tmp(perm ? rows * n : 0);
+  HIP_TRY(hipMemcpy2D(perm ? tmp.data() : out, n * sizeof(double), src,
+                      (size_t)q0.stride * sizeof(double), n * sizeof(double), rows,
+                      hipMemcpyDeviceToHost));
+  for (int kp = 0; kp < q0.n_p && perm; ++kp)
+    for (int kt = 0; kt < q0.n_T; ++kt)
+      std::memcpy(out + ((size_t)kp * q0.n_T + kt) * n,
+                  tmp.data() + ((size_t)kp * q0.n_T + c->kmix_rank[kt]) * n, n * sizeof(double));
+  return 0;
+}
+
 int frei_set_mmr(frei_ctx* c, const double* mmr) {
   if (!c || !mmr) return fail("null argument");
+  if (c->kmix_lib) {   // K20: every mixing ratio of a k-mix batch is 1 and stays 1
+    for (size_t i = 0; i < (size_t)c->nL * c->n_atm; ++i)
+      if (mmr[i] != 1.0)
+        return fail("frei_set_mmr: mmr[" + std::to_string(i) + "] = " + std::to_string(mmr[i]) +
+                    " on a k-mix batch: the compositions hold the mixing ratios");
+    return 0;
+  }
   const size_t n = (size_t)c->S * c->nL * c->n_atm;
   // A chemistry provider evaluated between sweeps (T-dependent, frei_amd Engine) sets new mixing
   // ratios before every sweep.  When the metadata is built and the sweep sums the species itself
@@ -1930,6 +2096,9 @@ int frei_set_chemistry_batch(frei_ctx* c, const double* values, int n_tab,
     c->meta_dirty = true;
     return 0;
   }
+  if (c->kmix_lib)
+    return fail("frei_set_chemistry_batch: the context holds a k-mix batch "
+                "(frei_set_table_kmix_batch); its compositions hold the mixing ratios");
   if (n_tab < 1) return fail("n_tab must be >= 1");
   if (!atm_tab) return fail("null atm_tab");
   for (int m = 0; m < c->n_atm; ++m)

@@ -183,6 +183,25 @@ class Instrument(DeviceObject):
             return tw[a:b] * np.exp(-0.5 * (z * z))
         return cls._build(lam, spans, weights_of, "holds no point of the axis", device, False)
 
+    def for_columns(self, n_g, weights):
+        """The instrument on the columns of a k-distribution (K20): the axis is
+        ``repeat(lam, n_g)`` (column ``b * n_g + q`` is bin b at g-point q), channel k covers the
+        columns of its bins — ``first * n_g``, ``count * n_g`` — and column (b, q) weighs
+        ``W_b w_q``: ``repeat(w_chan, n_g) * tile(weights, count)``.  With per-wavelength ``num``
+        and ``den`` repeated onto the columns, x on the columns gives
+        ``sum_b W_b sum_q w_q x_bq num_b / sum_b W_b sum_q w_q den_b``: the band value of the
+        collapsed spectrum up to rounding, which never has to exist on the device.  Host plan
+        construction only."""
+        w_q = N.f64(np.atleast_1d(weights))
+        n_g = int(n_g)
+        if n_g < 1 or w_q.shape != (n_g,):
+            raise ValueError(f"weights must be [n_g = {n_g}], one per quadrature point")
+        if not np.all(np.isfinite(w_q) & (w_q > 0)):
+            raise ValueError("the quadrature weights must be finite and positive")
+        return Instrument(np.repeat(self.lam, n_g), self.first * n_g, self.count * n_g,
+                          np.repeat(self.weights, n_g) * np.tile(w_q, self.weights.size),
+                          device=self.device)
+
     # ------------------------------------------------------------------ device
     def _create(self, h):
         """frei_obs* of the instrument (plan and weights uploaded once)."""

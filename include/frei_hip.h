@@ -640,6 +640,50 @@ int frei_klib_mix(frei_klib* lib, int n_comp, const double* x, double* out, int 
 int frei_set_table_kmix(frei_ctx* ctx, int s, frei_klib* lib, const double* x, int64_t col_lo);
 
 /*
+ * K20: a batch of correlated-k atmospheres, one composition each.  A batched context shares its
+ * species tables between atmospheres and forms each atmosphere's table as the linear species sum
+ * K7; the k(g) of several species do not add, so a k-mix batch keeps one mixed table per
+ * atmosphere instead, in the slot K7 writes ([n_atm][n_p][n_T][pitch], the only table the batched
+ * sweeps read), filled by K19's kernels.
+ *
+ * frei_set_table_kmix_batch: ctx comes from frei_ctx_create_batch with n_species = 1, after
+ * frei_set_grid; x is [n_atm][n_src][n_p][n_T], frei_klib_mix's layout.  Species 0 gets the
+ * library's nodes and composition 0's mixture (as frei_set_table_kmix writes it), the context
+ * records the library and a copy of x, and every mixing ratio becomes 1.  Each time the context
+ * builds its per-atmosphere tables (in this call, and after any call that rebuilds the metadata),
+ * atmosphere m's table is the random-overlap mixture of x[m] on the library's nodes, columns
+ * [col_lo, col_lo + n_lam): bitwise what frei_klib_mix returns for that composition, written
+ * straight into the table (K7 is not launched).  As for K7 only the pressure rows some layer sits
+ * on are mixed; the other rows, the column padding up to the pitch and each atmosphere's
+ * 64-element tail are zero.  A context with n_atm = 1 sweeps species 0's table: composition 0.
+ * Everything that runs on a batched context runs unchanged afterwards.  The library must outlive
+ * the context's use of it (the context keeps the pointer, not the library).
+ *
+ * frei_kmix_batch_update: new compositions x[n][n_src][n_p][n_T] for the atmospheres
+ * [atm_lo, atm_lo + n).  Only their rows are mixed again, in place, on the context's stream: no
+ * metadata rebuild, no allocation of a table; the other atmospheres' tables keep their bits.  The
+ * step a retrieval loop repeats.
+ *
+ * frei_get_table_batch: out[n_p][n_T][n_lam] is atmosphere atm's table as the sweeps read it
+ * (tests, diagnostics).  On a k-mix batch T is in the library's node order; on any other batched
+ * context with a per-atmosphere table it is ascending, as the table is stored.
+ *
+ * Every argument error is found on the host before any device call and names the first offender:
+ * a null argument; a context not made by frei_ctx_create_batch, or with n_species != 1;
+ * frei_set_grid not yet called; columns outside the library's n_bins * n_g; a device mismatch; a
+ * slot that holds no table; an x that is not finite or is negative, named x[m][s][p][t] (m counts
+ * from the first composition passed); atm_lo / n or atm out of range; an update on a context that
+ * holds no k-mix batch.  frei_set_chemistry_batch on a k-mix batch and frei_set_table_kmix_batch
+ * on a chemistry batch are refused, and so is a frei_set_mmr with any value other than 1 ("the
+ * compositions hold the mixing ratios").  After mixing, a NaN in a row that a layer uses fails
+ * the call that mixed and names the atmosphere, as batched contexts refuse NaN tables.  Any
+ * frei_set_table* call on the context ends the k-mix batch.
+ */
+int frei_set_table_kmix_batch(frei_ctx* ctx, frei_klib* lib, const double* x, int64_t col_lo);
+int frei_kmix_batch_update(frei_ctx* ctx, int atm_lo, int n, const double* x);
+int frei_get_table_batch(frei_ctx* ctx, int atm, double* out);
+
+/*
  * Stellar spectrum binning (phoenix.py:13-17, 43-52).  A frei_sspec is a library of model
  * spectra on one shared wavelength axis: flux[n_spec][n_hi] float64 resident in HBM on
  * wl_hi[n_hi] (um, strictly ascending).
