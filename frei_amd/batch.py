@@ -18,7 +18,7 @@ from .binning import MixedKTables
 from .chemistry import ChemistryTable, chemistry
 from .constants import BAR, C, H, K_B, M_BAR_DEFAULT, SIGMA_SB, UM
 from .emergent import emergent_call, pick
-from .engine import EMIT, Engine, f_toa, planck_prefactor, quadrature_weights
+from .engine import EMIT, ContextBase, f_toa, planck_prefactor, quadrature_weights
 from .opacity import sigma_scattering
 from .transit import default_radius, level_radii, transit_call
 from .units import scalar, value
@@ -100,7 +100,7 @@ def check_kmix(opacities, mmr, n_atm, n_lam, n_layers, device):
     return tabs
 
 
-class BatchEngine:
+class BatchEngine(ContextBase):
     """``n_atm`` atmospheres on ``device``: ``g`` [n_atm] (cm s^-2), ``mmr``
     [n_atm][n_species][n_layers], ``F_toa`` [n_lam] shared or [n_atm][n_lam] per atmosphere;
     wavelengths, pressures (bar, descending), opacities and m_bar are shared (as in a grid of
@@ -177,7 +177,7 @@ class BatchEngine:
                                                       N.dptr(self.kmix.x), self.lo))
             else:
                 for s, name in enumerate(self.names):
-                    Engine._set_table(self, s, opacities[name], slice(0, self.n_lam))
+                    self._set_table(s, opacities[name], slice(0, self.n_lam))
         except BaseException:
             self.close()
             raise
@@ -258,17 +258,6 @@ class BatchEngine:
         out = np.empty((nd.pressure.size, nd.temperature.size, self.n_lam))
         N.check(N.lib().frei_get_table_batch(self._ctx, int(m), N.dptr(out)))
         return out
-
-    def close(self):
-        if getattr(self, "_ctx", None):
-            N.lib().frei_ctx_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def run(self, T_init, n_timesteps=1, n_zero_crossings=2, convergence_dT=3.0, alpha=1.0,
             want_hist=False, keep_dtaus=False):
@@ -402,47 +391,16 @@ class BatchEngine:
         result on the device (:class:`~frei_amd.phasecurve.PhaseSpectra`)."""
         return pc.integrate(self, T, dtaus=dtaus, keep=keep)
 
-    def post_timing(self):
-        """HIP-event milliseconds of the kernels of the last :meth:`post`, :meth:`transit` or
-        :meth:`emergent` call."""
-        return Engine.post_timing(self)
-
     # fixed-work driver pieces (benchmarks)
     def state_init(self, T_init):
         T = N.f64(np.broadcast_to(np.asarray(T_init, dtype=float), (self.n_atm, self.n_layers)))
         N.check(N.lib().frei_state_init(self._ctx, N.dptr(T)))
-
-    def iterate(self, n, n_zero_crossings=-1, convergence_dT=3.0, alpha=1.0):
-        N.check(N.lib().frei_iterate(self._ctx, int(n), int(n_zero_crossings),
-                                     float(convergence_dT), float(alpha)))
-
-    def synchronize(self):
-        N.check(N.lib().frei_synchronize(self._ctx))
-
-    def timing(self, on):
-        N.check(N.lib().frei_timing_enable(self._ctx, 1 if on else 0))
-
-    def timing_read(self):
-        ms, n = ctypes.c_double(0), ctypes.c_int(0)
-        N.check(N.lib().frei_timing_read(self._ctx, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
-
-    def setup_timing(self):
-        return Engine.setup_timing(self)
-
-    def set_option(self, name, value):
-        return Engine.set_option(self, name, value)
-
-    def contract_timing(self):
-        return Engine.contract_timing(self)
 
     def get_fluxes(self):
         up = np.empty((self.n_atm, self.n_layers, self.n_lam))
         down = np.empty_like(up)
         N.check(N.lib().frei_get_fluxes(self._ctx, N.dptr(up), N.dptr(down)))
         return up, down
-
-    path = Engine.path
 
 
 BatchRecord = collections.namedtuple(

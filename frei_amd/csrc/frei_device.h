@@ -612,29 +612,26 @@ int kdist_into_table(frei_xsec* x, const double* wl_bins, int64_t n_bins, int n_
 }  // namespace frei
 struct frei_klib;
 namespace frei {
-// K19 (frei_kmix.hip): the checks of one composition x[n_src][n_p][n_T] of a library against the
-// columns [col_lo, col_lo + n_out) and a context's device, all on the host, and the library's
-// nodes (bar, K); then the mixture's columns into table rows d_tab + row_off[kp * n_T + kt].
+// K19 / K20 (frei_kmix.hip), the one interface between the runtime and the k-table library.
+// klib_batch_args: every argument check of n_comp compositions x[n_comp][n_src][n_p][n_T] of a
+// library against the columns [col_lo, col_lo + n_out) and a context's device, all on the host
+// (`me` prefixes the message; the single-table setter passes n_comp = 1), and the library's nodes
+// (bar, K).  kmix_rows_into: the columns of the listed rows of compositions already checked,
+// mixed into d_out on the stream st; it returns when st has finished.  One row of the list: node
+// `node` of composition `comp` goes to the row that starts at element `dst` of the destination
+// (a whole table of one composition: every node, comp = 0).
 struct KlibNodes {
   const double *p, *T;
   int n_p, n_T, n_src;
 };
-int klib_table_args(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_out, int device,
-                    KlibNodes* out);
-int kmix_into_table(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_out,
-                    const int64_t* row_off, double* d_tab);
-// K20: one row of a mix's row list — node `node` of composition `comp` goes to the row that
-// starts at element `dst` of the destination.  klib_batch_args checks n_comp compositions
-// x[n_comp][n_src][n_p][n_T] as klib_table_args checks one (`me` prefixes the message);
-// kmix_rows_into mixes the listed rows' columns [col_lo, col_lo + n_out) into d_out on the
-// stream st and returns when st has finished.
 struct KmixRow {
   int32_t comp, node;
   int64_t dst;
 };
 int klib_batch_args(const std::string& me, frei_klib* lib, int n_comp, const double* x,
                     int64_t col_lo, int64_t n_out, int device, KlibNodes* out);
-int kmix_rows_into(frei_klib* lib, int n_comp, const double* x, int64_t col_lo, int64_t n_out,
-                   const KmixRow* rows, size_t n_rows, double* d_out, hipStream_t st);
+int kmix_rows_into(const std::string& me, frei_klib* lib, int n_comp, const double* x,
+                   int64_t col_lo, int64_t n_out, const KmixRow* rows, size_t n_rows,
+                   double* d_out, hipStream_t st);
 
 }  // namespace frei

@@ -295,12 +295,8 @@ int env_form() {
   return -1;
 }
 
-// Every argument error of a mix, before any device call; *form becomes the form to launch.
-int check_mix(const std::string& me, const frei_klib* lib, int n_comp, const double* x,
-              int64_t col_lo, int64_t n_out, int* form) {
-  if (!lib) return set_error(me + "null library");
-  if (!x) return set_error(me + "null x");
-  if (n_comp < 1) return set_error(me + "n_comp < 1");
+// The form to launch for the request *form (0: FREI_KMIX_FORM, then by n_g), or its error.
+int choose_form(const std::string& me, const frei_klib* lib, int* form) {
   if (*form < 0 || *form > 2)
     return set_error(me + "form must be 0 (automatic), 1 (wave) or 2 (block)");
   if (*form == kAuto) *form = env_form();
@@ -309,6 +305,15 @@ int check_mix(const std::string& me, const frei_klib* lib, int n_comp, const dou
     return set_error(me + "the wave form takes n_g <= " + std::to_string(kWaveG) + ", not n_g = " +
                      std::to_string(lib->n_g));
   if (*form == kAuto) *form = lib->n_g <= kAutoWaveG ? kWave : kBlock;
+  return 0;
+}
+
+// Every argument error of a mix but the form's (choose_form), before any device call.
+int check_mix(const std::string& me, const frei_klib* lib, int n_comp, const double* x,
+              int64_t col_lo, int64_t n_out) {
+  if (!lib) return set_error(me + "null library");
+  if (!x) return set_error(me + "null x");
+  if (n_comp < 1) return set_error(me + "n_comp < 1");
   for (int s = 0; s < lib->n_src; ++s)
     if (!lib->set[s]) return set_error(me + "slot " + std::to_string(s) + " holds no table");
   const int64_t n_col = lib->n_bins * lib->n_g;
@@ -391,32 +396,11 @@ int mix_into(frei_klib* lib, int n_comp, const double* x, int64_t col_lo, int64_
 }  // namespace
 
 namespace frei {
-int klib_table_args(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_out, int device,
-                    KlibNodes* out) {
-  const std::string me = "frei_set_table_kmix: ";
-  int form = kAuto;
-  TRY(check_mix(me, lib, 1, x, col_lo, n_out, &form));
-  if (lib->device != device)
-    return set_error(me + "the library lives on device " + std::to_string(lib->device) +
-                     ", the context on device " + std::to_string(device));
-  *out = KlibNodes{lib->p.data(), lib->T.data(), lib->n_p, lib->n_T, lib->n_src};
-  return 0;
-}
-
-int kmix_into_table(frei_klib* lib, const double* x, int64_t col_lo, int64_t n_out,
-                    const int64_t* row_off, double* d_tab) {
-  int form = kAuto;
-  TRY(check_mix("frei_set_table_kmix: ", lib, 1, x, col_lo, n_out, &form));
-  HIP_TRY(hipSetDevice(lib->device));
-  const std::vector<KmixRow> rows = all_rows(1, lib->n_p * lib->n_T, row_off);
-  return mix_into(lib, 1, x, col_lo, n_out, rows.data(), rows.size(), d_tab, form, nullptr,
-                  lib->stream);
-}
-
 int klib_batch_args(const std::string& me, frei_klib* lib, int n_comp, const double* x,
                     int64_t col_lo, int64_t n_out, int device, KlibNodes* out) {
-  int form = kAuto;
-  TRY(check_mix(me, lib, n_comp, x, col_lo, n_out, &form));
+  int form = kAuto;   // (a bad FREI_KMIX_FORM is refused here too, before the context changes)
+  TRY(check_mix(me, lib, n_comp, x, col_lo, n_out));
+  TRY(choose_form(me, lib, &form));
   if (lib->device != device)
     return set_error(me + "the library lives on device " + std::to_string(lib->device) +
                      ", the context on device " + std::to_string(device));
@@ -424,10 +408,11 @@ int klib_batch_args(const std::string& me, frei_klib* lib, int n_comp, const dou
   return 0;
 }
 
-int kmix_rows_into(frei_klib* lib, int n_comp, const double* x, int64_t col_lo, int64_t n_out,
-                   const KmixRow* rows, size_t n_rows, double* d_out, hipStream_t st) {
+int kmix_rows_into(const std::string& me, frei_klib* lib, int n_comp, const double* x,
+                   int64_t col_lo, int64_t n_out, const KmixRow* rows, size_t n_rows,
+                   double* d_out, hipStream_t st) {
   int form = kAuto;
-  TRY(check_mix("frei_kmix_batch_update: ", lib, n_comp, x, col_lo, n_out, &form));
+  TRY(choose_form(me, lib, &form));
   if (n_rows == 0) return 0;
   return mix_into(lib, n_comp, x, col_lo, n_out, rows, n_rows, d_out, form, nullptr, st);
 }
@@ -567,7 +552,8 @@ int frei_klib_mix(frei_klib* lib, int n_comp, const double* x, double* out, int 
   const std::string me = "frei_klib_mix: ";
   if (kernel_ms) *kernel_ms = 0.0;
   const int64_t n_col = lib ? lib->n_bins * lib->n_g : 0;
-  TRY(check_mix(me, lib, n_comp, x, 0, n_col, &form));
+  TRY(check_mix(me, lib, n_comp, x, 0, n_col));
+  TRY(choose_form(me, lib, &form));
   const size_t rows = (size_t)n_comp * lib->n_p * lib->n_T, total = rows * (size_t)n_col;
   HIP_TRY(hipSetDevice(lib->device));
   if (lib->out_cap < total) {

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -77,7 +78,13 @@ struct Species {
   int has_nan = 1;     // set by a device scan after upload/generation
   int64_t stride = 0;  // row pitch in elements (n_lam rounded up to 64, zero padded)
   std::vector<double> p_nodes, T_nodes;
+  std::vector<int32_t> rank;   // [n_T] storage row (T ascending) of the caller's node kt
 };
+
+// Element offset in q's table of the row of the caller's node (kp, kt).
+int64_t node_offset(const Species& q, int kp, int kt) {
+  return ((int64_t)kp * q.n_T + q.rank[kt]) * q.stride;
+}
 
 }  // namespace
 
@@ -278,7 +285,6 @@ struct frei_ctx {
   std::vector<double> kmix_x;        // [n_atm][n_src][n_p][n_T]
   int64_t kmix_col_lo = 0;
   int kmix_nsrc = 0;
-  std::vector<int32_t> kmix_rank;    // [n_T] storage row (ascending T) of the library's node kt
   std::vector<char> kmix_used;       // [n_p] a layer sits on the row (the last metadata build)
   // P2P exchange over xGMI (frei_comm_p2p_*): own mailbox (uncached device memory), the
   // mapped mailboxes of every rank (own included) and the per-sweep sequence number
@@ -402,11 +408,27 @@ int atm_tile_width(const frei_ctx* c, bool shared_nodes) {
   return t;
 }
 
+// Device NaN scan of n tables of len elements, table i at base + i * stride, on the context's
+// stream: flag[i] (host) becomes nonzero when table i holds a NaN.  Returns when the stream has
+// finished.
+int scan_tables(frei_ctx* c, const double* base, size_t stride, int64_t len, int n, int* flag) {
+  DeviceCall call(c->stream, "NaN scan");
+  int* d_flag = call.alloc<int>((size_t)n);
+  if (call.ok() && hipMemsetAsync(d_flag, 0, (size_t)n * sizeof(int), c->stream) != hipSuccess)
+    call.check(fail("NaN scan: clearing the flags failed"));
+  for (int i = 0; i < n && call.ok(); ++i)
+    launch_nan_scan(base + (size_t)i * stride, len, d_flag + i, c->stream);
+  call.end();
+  call.download(flag, d_flag, (size_t)n);
+  return call.finish();
+}
+
 // K20: the tables of the atmospheres [atm_lo, atm_lo + n) of a k-mix batch mixed into d_eff on
-// the context's stream, each (used pressure row, T node) a row of K19's list; then a NaN in any
-// of them fails the call and names the first atmosphere.  The rest of each table (the other
-// rows, the column padding, the tail) is zero since the metadata build and is not touched.
-int kmix_fill(frei_ctx* c, int atm_lo, int n) {
+// the context's stream, each (used pressure row, T node) a row of K19's list (`me` prefixes the
+// mixer's messages); then a NaN in any of them fails the call and names the first atmosphere.
+// The rest of each table (the other rows, the column padding, the tail) is zero since the
+// metadata build and is not touched.
+int kmix_fill(frei_ctx* c, int atm_lo, int n, const std::string& me) {
   const Species& q0 = c->sp[0];
   std::vector<KmixRow> rows;
   for (int i = 0; i < n; ++i)
@@ -414,25 +436,13 @@ int kmix_fill(frei_ctx* c, int atm_lo, int n) {
       for (int kt = 0; kt < q0.n_T && c->kmix_used[kp]; ++kt)
         rows.push_back(KmixRow{i, kp * q0.n_T + kt,
                                (int64_t)((size_t)(atm_lo + i) * c->eff_stride) +
-                                   ((int64_t)kp * q0.n_T + c->kmix_rank[kt]) * q0.stride});
+                                   node_offset(q0, kp, kt)});
   const size_t per_x = (size_t)c->kmix_nsrc * q0.n_p * q0.n_T;
-  TRY(kmix_rows_into(c->kmix_lib, n, c->kmix_x.data() + (size_t)atm_lo * per_x, c->kmix_col_lo,
-                     c->nlam, rows.data(), rows.size(), c->d_eff, c->stream));
-  int* d_flag = nullptr;
-  TRY(dalloc(&d_flag, (size_t)n));
+  TRY(kmix_rows_into(me, c->kmix_lib, n, c->kmix_x.data() + (size_t)atm_lo * per_x,
+                     c->kmix_col_lo, c->nlam, rows.data(), rows.size(), c->d_eff, c->stream));
   std::vector<int> flag((size_t)n, 0);
-  int rc = 0;
-  if (hipMemsetAsync(d_flag, 0, (size_t)n * sizeof(int), c->stream) != hipSuccess) rc = 1;
-  for (int i = 0; i < n && !rc; ++i)
-    launch_nan_scan(c->d_eff + (size_t)(atm_lo + i) * c->eff_stride,
-                    (int64_t)q0.n_p * q0.n_T * q0.stride, d_flag + i, c->stream);
-  if (!rc && (hipGetLastError() != hipSuccess ||
-              hipMemcpyAsync(flag.data(), d_flag, (size_t)n * sizeof(int), hipMemcpyDeviceToHost,
-                             c->stream) != hipSuccess ||
-              hipStreamSynchronize(c->stream) != hipSuccess))
-    rc = 1;
-  dfree(d_flag);
-  if (rc) return fail("the NaN scan of the mixed tables failed");
+  TRY(scan_tables(c, c->d_eff + (size_t)atm_lo * c->eff_stride, c->eff_stride,
+                  (int64_t)q0.n_p * q0.n_T * q0.stride, n, flag.data()));
   for (int i = 0; i < n; ++i)
     if (flag[i])
       return fail("the mixed table of atmosphere " + std::to_string(atm_lo + i) +
@@ -557,7 +567,7 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
     return fail("hipEventCreate failed");
   HIP_TRY(hipEventRecord(k0, c->stream));
   if (kmix) {               // K20: K19's random-overlap mixture per atmosphere, not a species sum
-    const int rc = kmix_fill(c, 0, c->n_atm);
+    const int rc = kmix_fill(c, 0, c->n_atm, "k-mix batch tables: ");
     if (rc) {
       (void)hipEventDestroy(k0);
       (void)hipEventDestroy(k1);
@@ -1733,6 +1743,10 @@ static std::vector<int32_t> t_order(const double* T_nodes, int n_T) {
   return perm;
 }
 
+// Begins species s's table on the nodes (dyn cm^-2, K; T in any order): sized, zeroed, the nodes
+// recorded with T ascending and the row order in q.rank.  Every setter starts here (the table
+// path: DESIGN.md, "Table path of the opacity setters"), writes the rows at node_offset() and
+// ends in scan_nan().
 static int set_table_common(frei_ctx* c, int s, const double* p_nodes, int n_p,
                             const double* T_nodes, int n_T) {
   if (s < 0 || s >= c->S) return fail("species index out of range");
@@ -1758,7 +1772,11 @@ static int set_table_common(frei_ctx* c, int s, const double* p_nodes, int n_p,
   q.p_nodes.assign(p_nodes, p_nodes + n_p);
   const std::vector<int32_t> perm = t_order(T_nodes, n_T);
   q.T_nodes.resize(n_T);
-  for (int t = 0; t < n_T; ++t) q.T_nodes[t] = T_nodes[perm[t]];  // stored ascending
+  q.rank.resize(n_T);
+  for (int t = 0; t < n_T; ++t) {
+    q.T_nodes[t] = T_nodes[perm[t]];  // stored ascending
+    q.rank[perm[t]] = t;
+  }
   c->kmix_lib = nullptr;   // a new table ends a k-mix batch (frei_set_table_kmix_batch sets it after)
   c->meta_dirty = true;
   return 0;
@@ -1768,15 +1786,8 @@ static int set_table_common(frei_ctx* c, int s, const double* p_nodes, int n_p,
 // reference's nansum (Q8) when no table can produce a NaN.
 static int scan_nan(frei_ctx* c, int s) {
   Species& q = c->sp[s];
-  int* d_flag = nullptr;
-  TRY(dalloc(&d_flag, 1));
-  HIP_TRY(hipMemsetAsync(d_flag, 0, sizeof(int), c->stream));
-  launch_nan_scan(q.d_tab, (int64_t)q.n_p * q.n_T * q.stride, d_flag, c->stream);
-  HIP_TRY(hipGetLastError());
   int h = 1;
-  HIP_TRY(hipMemcpyAsync(&h, d_flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  dfree(d_flag);
+  TRY(scan_tables(c, q.d_tab, 0, (int64_t)q.n_p * q.n_T * q.stride, 1, &h));
   q.has_nan = h;
   return 0;
 }
@@ -1786,20 +1797,18 @@ int frei_set_table(frei_ctx* c, int s, const double* values, const double* p_nod
   if (!c || !values || !p_nodes || !T_nodes) return fail("null argument");
   TRY(set_device(c));
   TRY(set_table_common(c, s, p_nodes, n_p, T_nodes, n_T));
-  const std::vector<int32_t> perm = t_order(T_nodes, n_T);
+  const Species& q = c->sp[s];
   bool ident = true;
-  for (int t = 0; t < n_T; ++t) ident = ident && perm[t] == t;
+  for (int t = 0; t < n_T; ++t) ident = ident && q.rank[t] == t;
   const size_t row = (size_t)c->nlam;
-  const size_t pitch = (size_t)c->sp[s].stride * sizeof(double);
   if (ident) {
-    HIP_TRY(hipMemcpy2D(c->sp[s].d_tab, pitch, values, row * sizeof(double),
+    HIP_TRY(hipMemcpy2D(q.d_tab, (size_t)q.stride * sizeof(double), values, row * sizeof(double),
                         row * sizeof(double), (size_t)n_p * n_T, hipMemcpyHostToDevice));
   } else {
-    for (int p = 0; p < n_p; ++p)
-      for (int t = 0; t < n_T; ++t)
-        HIP_TRY(hipMemcpy(c->sp[s].d_tab + ((size_t)p * n_T + t) * c->sp[s].stride,
-                          values + ((size_t)p * n_T + perm[t]) * row, row * sizeof(double),
-                          hipMemcpyHostToDevice));
+    for (int kp = 0; kp < n_p; ++kp)
+      for (int kt = 0; kt < n_T; ++kt)
+        HIP_TRY(hipMemcpy(q.d_tab + node_offset(q, kp, kt), values + ((size_t)kp * n_T + kt) * row,
+                          row * sizeof(double), hipMemcpyHostToDevice));
   }
   return scan_nan(c, s);
 }
@@ -1810,80 +1819,84 @@ int frei_set_table_separable(frei_ctx* c, int s, const double* base, const doubl
   if (!c || !base || !fp || !fT || !p_nodes || !T_nodes) return fail("null argument");
   TRY(set_device(c));
   TRY(set_table_common(c, s, p_nodes, n_p, T_nodes, n_T));
-  const std::vector<int32_t> perm = t_order(T_nodes, n_T);
-  std::vector<double> fT_sorted(n_T);
-  for (int t = 0; t < n_T; ++t) fT_sorted[t] = fT[perm[t]];
-  fT = fT_sorted.data();
-  double *d_base = nullptr, *d_fp = nullptr, *d_fT = nullptr;
-  TRY(dalloc(&d_base, c->nlam));
-  TRY(dalloc(&d_fp, n_p));
-  TRY(dalloc(&d_fT, n_T));
-  TRY(h2d_wait(d_base, base, c->nlam, c->stream));
-  TRY(h2d_wait(d_fp, fp, n_p, c->stream));
-  TRY(h2d_wait(d_fT, fT, n_T, c->stream));
-  launch_gen_table(c->sp[s].d_tab, d_base, d_fp, d_fT, n_p, n_T, c->nlam, c->sp[s].stride, lo,
-                   hi, c->stream);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  dfree(d_base);
-  dfree(d_fp);
-  dfree(d_fT);
+  const Species& q = c->sp[s];
+  std::vector<double> fT_sorted(n_T);   // (outlives finish(): the uploads are queued)
+  for (int t = 0; t < n_T; ++t) fT_sorted[q.rank[t]] = fT[t];
+  DeviceCall call(c->stream, "separable table");
+  const double* d_base = call.upload(base, (size_t)c->nlam);
+  const double* d_fp = call.upload(fp, (size_t)n_p);
+  const double* d_fT = call.upload(fT_sorted.data(), (size_t)n_T);
+  if (call.ok())
+    launch_gen_table(q.d_tab, d_base, d_fp, d_fT, n_p, n_T, c->nlam, q.stride, lo, hi, c->stream);
+  call.end();
+  TRY(call.finish());
   return scan_nan(c, s);
 }
 
-// Element offset in species s's table of the row of target node (kp, kt), [n_p * n_T]: the T
-// axis is stored ascending (the device binning calls write their rows there).
-static std::vector<int64_t> node_row_offsets(frei_ctx* c, int s, const double* T_nodes, int n_T,
-                                             int n_p) {
-  const std::vector<int32_t> perm = t_order(T_nodes, n_T);
-  std::vector<int32_t> rank(n_T);
-  for (int t = 0; t < n_T; ++t) rank[perm[t]] = t;
-  std::vector<int64_t> row_off((size_t)n_p * n_T);
-  for (int kp = 0; kp < n_p; ++kp)
-    for (int kt = 0; kt < n_T; ++kt)
-      row_off[(size_t)kp * n_T + kt] = ((int64_t)kp * n_T + rank[kt]) * c->sp[s].stride;
+// Element offset in q's table of the row of every node (kp, kt) of the caller, [n_p * n_T].
+static std::vector<int64_t> node_row_offsets(const Species& q) {
+  std::vector<int64_t> row_off((size_t)q.n_p * q.n_T);
+  for (int kp = 0; kp < q.n_p; ++kp)
+    for (int kt = 0; kt < q.n_T; ++kt) row_off[(size_t)kp * q.n_T + kt] = node_offset(q, kp, kt);
   return row_off;
+}
+
+// The one body of the setters whose table the device writes (K6, K18, K19): species s's table on
+// the nodes p_bar (bar) and T_nodes (K, any order) is begun, fill(row_off, d_tab) writes the row
+// of node (kp, kt) at d_tab + row_off[kp * n_T + kt] and returns when it is complete, and the
+// table is scanned for NaN.
+using TableFill = std::function<int(const int64_t* row_off, double* d_tab)>;
+static int set_table_filled(frei_ctx* c, int s, const double* p_bar, int n_p,
+                            const double* T_nodes, int n_T, const TableFill& fill) {
+  TRY(set_device(c));
+  std::vector<double> p_cgs(n_p > 0 ? n_p : 0);
+  for (int k = 0; k < n_p; ++k) p_cgs[k] = p_bar[k] * 1e6;  // bar -> dyn cm^-2
+  TRY(set_table_common(c, s, p_cgs.data(), n_p, T_nodes, n_T));
+  TRY(fill(node_row_offsets(c->sp[s]).data(), c->sp[s].d_tab));
+  return scan_nan(c, s);
 }
 
 int frei_set_table_binned(frei_ctx* c, int s, frei_xsec* x, int mode, const double* wl_bins,
                           const double* lam, int64_t n_bins, int64_t lam_lo,
                           const double* T_nodes, int n_T, const double* p_nodes, int n_p) {
   if (!c || !x || !wl_bins || !lam || !T_nodes || !p_nodes) return fail("null argument");
-  TRY(set_device(c));
-  std::vector<double> p_cgs(n_p > 0 ? n_p : 0);
-  for (int k = 0; k < n_p; ++k) p_cgs[k] = p_nodes[k] * 1e6;  // bar -> dyn cm^-2
-  TRY(set_table_common(c, s, p_cgs.data(), n_p, T_nodes, n_T));
-  const std::vector<int64_t> row_off = node_row_offsets(c, s, T_nodes, n_T, n_p);
-  TRY(bin_into_table(x, mode, wl_bins, lam, n_bins, lam_lo, c->nlam, T_nodes, n_T, p_nodes,
-                     n_p, row_off.data(), c->sp[s].d_tab, c->device));
-  return scan_nan(c, s);
+  return set_table_filled(c, s, p_nodes, n_p, T_nodes, n_T,
+                          [&](const int64_t* row_off, double* d_tab) {
+    return bin_into_table(x, mode, wl_bins, lam, n_bins, lam_lo, c->nlam, T_nodes, n_T, p_nodes,
+                          n_p, row_off, d_tab, c->device);
+  });
 }
 
 int frei_set_table_kdist(frei_ctx* c, int s, frei_xsec* x, const double* wl_bins, int64_t n_bins,
                          int n_g, const double* g, const double* T_nodes, int n_T,
                          const double* p_nodes, int n_p, int64_t col_lo) {
   if (!c || !x || !wl_bins || !g || !T_nodes || !p_nodes) return fail("null argument");
-  TRY(set_device(c));
-  std::vector<double> p_cgs(n_p > 0 ? n_p : 0);
-  for (int k = 0; k < n_p; ++k) p_cgs[k] = p_nodes[k] * 1e6;  // bar -> dyn cm^-2
-  TRY(set_table_common(c, s, p_cgs.data(), n_p, T_nodes, n_T));
-  const std::vector<int64_t> row_off = node_row_offsets(c, s, T_nodes, n_T, n_p);
-  TRY(kdist_into_table(x, wl_bins, n_bins, n_g, g, col_lo, c->nlam, T_nodes, n_T, p_nodes, n_p,
-                       row_off.data(), c->sp[s].d_tab, c->device));
-  return scan_nan(c, s);
+  return set_table_filled(c, s, p_nodes, n_p, T_nodes, n_T,
+                          [&](const int64_t* row_off, double* d_tab) {
+    return kdist_into_table(x, wl_bins, n_bins, n_g, g, col_lo, c->nlam, T_nodes, n_T, p_nodes,
+                            n_p, row_off, d_tab, c->device);
+  });
+}
+
+// K19's fill of a whole table: every node of the one composition x (already checked), on the
+// context's stream (the library's tables are complete when frei_klib_set* return).
+static TableFill kmix_table_fill(frei_ctx* c, const std::string& me, frei_klib* lib,
+                                 const double* x, int64_t col_lo, int n_nodes) {
+  return [=](const int64_t* row_off, double* d_tab) {
+    std::vector<KmixRow> rows((size_t)n_nodes);
+    for (int nd = 0; nd < n_nodes; ++nd) rows[nd] = KmixRow{0, nd, row_off[nd]};
+    return kmix_rows_into(me, lib, 1, x, col_lo, c->nlam, rows.data(), rows.size(), d_tab,
+                          c->stream);
+  };
 }
 
 int frei_set_table_kmix(frei_ctx* c, int s, frei_klib* lib, const double* x, int64_t col_lo) {
+  const std::string me = "frei_set_table_kmix: ";
   if (!c || !lib || !x) return fail("null argument");
   KlibNodes nd{};
-  TRY(klib_table_args(lib, x, col_lo, c->nlam, c->device, &nd));
-  TRY(set_device(c));
-  std::vector<double> p_cgs(nd.n_p);
-  for (int k = 0; k < nd.n_p; ++k) p_cgs[k] = nd.p[k] * 1e6;  // bar -> dyn cm^-2
-  TRY(set_table_common(c, s, p_cgs.data(), nd.n_p, nd.T, nd.n_T));
-  const std::vector<int64_t> row_off = node_row_offsets(c, s, nd.T, nd.n_T, nd.n_p);
-  TRY(kmix_into_table(lib, x, col_lo, c->nlam, row_off.data(), c->sp[s].d_tab));
-  return scan_nan(c, s);
+  TRY(klib_batch_args(me, lib, 1, x, col_lo, c->nlam, c->device, &nd));
+  return set_table_filled(c, s, nd.p, nd.n_p, nd.T, nd.n_T,
+                          kmix_table_fill(c, me, lib, x, col_lo, nd.n_p * nd.n_T));
 }
 
 int frei_set_table_kmix_batch(frei_ctx* c, frei_klib* lib, const double* x, int64_t col_lo) {
@@ -1899,16 +1912,9 @@ int frei_set_table_kmix_batch(frei_ctx* c, frei_klib* lib, const double* x, int6
                      "batch's compositions hold the mixing ratios");
   KlibNodes nd{};
   TRY(klib_batch_args(me, lib, c->n_atm, x, col_lo, c->nlam, c->device, &nd));
-  TRY(set_device(c));
-  std::vector<double> p_cgs(nd.n_p);
-  for (int k = 0; k < nd.n_p; ++k) p_cgs[k] = nd.p[k] * 1e6;  // bar -> dyn cm^-2
-  TRY(set_table_common(c, 0, p_cgs.data(), nd.n_p, nd.T, nd.n_T));
-  const std::vector<int64_t> row_off = node_row_offsets(c, 0, nd.T, nd.n_T, nd.n_p);
-  TRY(kmix_into_table(lib, x, col_lo, c->nlam, row_off.data(), c->sp[0].d_tab));
-  TRY(scan_nan(c, 0));
-  const std::vector<int32_t> perm = t_order(nd.T, nd.n_T);
-  c->kmix_rank.assign(nd.n_T, 0);
-  for (int t = 0; t < nd.n_T; ++t) c->kmix_rank[perm[t]] = t;
+  // species 0: the nodes and composition 0's mixture
+  TRY(set_table_filled(c, 0, nd.p, nd.n_p, nd.T, nd.n_T,
+                       kmix_table_fill(c, me, lib, x, col_lo, nd.n_p * nd.n_T)));
   c->kmix_x.assign(x, x + (size_t)c->n_atm * nd.n_src * nd.n_p * nd.n_T);
   c->kmix_col_lo = col_lo;
   c->kmix_nsrc = nd.n_src;
@@ -1932,20 +1938,17 @@ int frei_kmix_batch_update(frei_ctx* c, int atm_lo, int n, const double* x) {
   const Species& q0 = c->sp[0];
   const size_t per_x = (size_t)c->kmix_nsrc * q0.n_p * q0.n_T;
   std::copy(x, x + (size_t)n * per_x, c->kmix_x.begin() + (size_t)atm_lo * per_x);
-  if (c->n_atm == 1) {   // the one atmosphere sweeps species 0's table: re-mixed in place
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    std::vector<int64_t> row_off((size_t)q0.n_p * q0.n_T);
-    for (int kp = 0; kp < q0.n_p; ++kp)
-      for (int kt = 0; kt < q0.n_T; ++kt)
-        row_off[(size_t)kp * q0.n_T + kt] = ((int64_t)kp * q0.n_T + c->kmix_rank[kt]) * q0.stride;
-    TRY(kmix_into_table(c->kmix_lib, x, c->kmix_col_lo, c->nlam, row_off.data(), q0.d_tab));
+  if (c->n_atm == 1) {   // the one atmosphere sweeps species 0's table: re-mixed in place, on the
+                         // context's stream behind the sweeps that still read it
+    const TableFill remix = kmix_table_fill(c, me, c->kmix_lib, x, c->kmix_col_lo, q0.n_p * q0.n_T);
+    TRY(remix(node_row_offsets(q0).data(), q0.d_tab));
     const int had = q0.has_nan;
     TRY(scan_nan(c, 0));
     if (c->sp[0].has_nan != had) c->meta_dirty = true;   // the sweep's NaN skip changes
     return 0;
   }
   if (c->meta_dirty) return 0;   // the next metadata build mixes every atmosphere
-  const int rc = kmix_fill(c, atm_lo, n);
+  const int rc = kmix_fill(c, atm_lo, n, me);
   if (rc) c->meta_dirty = true;   // no run on a table that holds a NaN
   return rc;
 }
@@ -1966,15 +1969,18 @@ int frei_get_table_batch(frei_ctx* c, int atm, double* out) {
   const double* src = c->eff ? c->d_eff + (size_t)atm * c->eff_stride : q0.d_tab;
   const size_t rows = (size_t)q0.n_p * q0.n_T, n = (size_t)c->nlam;
   HIP_TRY(hipStreamSynchronize(c->stream));
-  const bool perm = c->kmix_lib != nullptr;
-  std::vector<double> tmp(perm ? rows * n : 0);
-  HIP_TRY(hipMemcpy2D(perm ? tmp.data() : out, n * sizeof(double), src,
-                      (size_t)q0.stride * sizeof(double), n * sizeof(double), rows,
-                      hipMemcpyDeviceToHost));
-  for (int kp = 0; kp < q0.n_p && perm; ++kp)
+  if (!c->kmix_lib) {   // as stored: T ascending
+    HIP_TRY(hipMemcpy2D(out, n * sizeof(double), src, (size_t)q0.stride * sizeof(double),
+                        n * sizeof(double), rows, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  // a k-mix batch: the rows in the library's node order
+  std::vector<double> tmp(rows * (size_t)q0.stride);
+  HIP_TRY(hipMemcpy(tmp.data(), src, tmp.size() * sizeof(double), hipMemcpyDeviceToHost));
+  for (int kp = 0; kp < q0.n_p; ++kp)
     for (int kt = 0; kt < q0.n_T; ++kt)
-      std::memcpy(out + ((size_t)kp * q0.n_T + kt) * n,
-                  tmp.data() + ((size_t)kp * q0.n_T + c->kmix_rank[kt]) * n, n * sizeof(double));
+      std::memcpy(out + ((size_t)kp * q0.n_T + kt) * n, tmp.data() + node_offset(q0, kp, kt),
+                  n * sizeof(double));
   return 0;
 }
 
@@ -2006,12 +2012,10 @@ int frei_set_ftoa_batch(frei_ctx* c, const double* f_toa) {
   if (!c->grid_set) return fail("frei_set_grid must be called first");
   TRY(set_device(c));
   const size_t n = (size_t)c->nlam * c->n_atm;
-  double* d = nullptr;
-  TRY(dalloc(&d, n));
-  if (h2d_wait(d, f_toa, n, c->stream) || hipStreamSynchronize(c->stream) != hipSuccess) {
-    dfree(d);
-    return fail("F_TOA upload failed");
-  }
+  DeviceCall call(c->stream, "F_TOA upload");
+  double* d = call.upload(f_toa, n);
+  call.keep(d);
+  TRY(call.finish());   // (queued sweeps have finished with the old F_TOA too)
   dfree(c->d_ftoa);
   c->d_ftoa = d;
   c->ftoa_per_atm = true;

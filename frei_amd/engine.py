@@ -110,7 +110,119 @@ def device_key(device):
     return f"{socket.gethostname()}|{buf.value.decode()}"
 
 
-class Engine:
+class ContextBase:
+    """What :class:`Engine` and :class:`~frei_amd.batch.BatchEngine` share: the context handle
+    ``_ctx`` (one ``frei_ctx``) and the calls whose arguments do not depend on the number of
+    atmospheres.  A subclass creates the context and sets ``lam_um``, ``lo``, ``device``."""
+
+    _ctx = None
+
+    def close(self):
+        if self._ctx:
+            N.lib().frei_ctx_destroy(self._ctx)
+            self._ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _set_table(self, s, tab, sl):
+        """Species ``s``'s table from ``tab``, by its kind; ``sl`` is the context's slice of the
+        grid's wavelength axis (host tables are cut to it, device tables written for it)."""
+        lib = N.lib()
+        p, T = _table_arrays(tab)
+        p_cgs, T = N.f64(p * BAR), N.f64(T)
+        if isinstance(tab, (BinnedTable, KTable, MixedKTable)):   # written on the device
+            if tab.wavelength.size != self.lam_um.size:
+                raise ValueError("binned table wavelengths must match the grid"
+                                 if isinstance(tab, BinnedTable) else
+                                 "k-table columns (n_bins * n_g) must match the grid's columns")
+        if isinstance(tab, BinnedTable):
+            N.check(lib.frei_set_table_binned(
+                self._ctx, s, tab.xsec.handle(self.device), tab.mode, N.dptr(tab.wl_bins),
+                N.dptr(tab.wavelength), tab.wavelength.size, self.lo, N.dptr(tab.temperature),
+                tab.temperature.size, N.dptr(tab.pressure), tab.pressure.size))
+        elif isinstance(tab, KTable):
+            N.check(lib.frei_set_table_kdist(
+                self._ctx, s, tab.xsec.handle(self.device), N.dptr(tab.wl_bins), tab.n_bins,
+                tab.g.size, N.dptr(tab.g), N.dptr(tab.temperature), tab.temperature.size,
+                N.dptr(tab.pressure), tab.pressure.size, self.lo))
+        elif isinstance(tab, MixedKTable):
+            if tab.device != self.device:
+                raise ValueError(f"the k-table library lives on device {tab.device}, the engine "
+                                 f"on device {self.device}")
+            N.check(lib.frei_set_table_kmix(self._ctx, s, tab.library.handle(), N.dptr(tab.x),
+                                            self.lo))
+        elif isinstance(tab, SeparableTable):
+            N.check(lib.frei_set_table_separable(
+                self._ctx, s, N.dptr(N.f64(tab.base[sl])), N.dptr(N.f64(tab.fp)),
+                N.dptr(N.f64(tab.fT)), tab.lo, tab.hi, N.dptr(p_cgs), p.size, N.dptr(T), T.size))
+        else:
+            vals = table_values(tab)      # transposed by name when the table carries .dims
+            if vals.ndim != 3 or vals.shape[:2] != (p.size, T.size):
+                raise ValueError("opacity table must be (pressure, temperature, wavelength)")
+            if vals.shape[2] != self.lam_um.size:
+                raise ValueError("opacity table wavelength axis must match the grid")
+            v = N.f64(vals[:, :, sl])
+            N.check(lib.frei_set_table(self._ctx, s, N.dptr(v), N.dptr(p_cgs), p.size,
+                                       N.dptr(T), T.size))
+
+    def iterate(self, n, n_zero_crossings=-1, convergence_dT=3.0, alpha=1.0):
+        N.check(N.lib().frei_iterate(self._ctx, int(n), int(n_zero_crossings),
+                                     float(convergence_dT), float(alpha)))
+
+    def synchronize(self):
+        N.check(N.lib().frei_synchronize(self._ctx))
+
+    def timing(self, on):
+        N.check(N.lib().frei_timing_enable(self._ctx, 1 if on else 0))
+
+    def timing_read(self):
+        ms = ctypes.c_double(0)
+        n = ctypes.c_int(0)
+        N.check(N.lib().frei_timing_read(self._ctx, ctypes.byref(ms), ctypes.byref(n)))
+        return ms.value, n.value
+
+    def path(self):
+        """Sweep implementation the tables select: dict(fast, lds_steps, contracted, nan)."""
+        f = ctypes.c_int(0)
+        N.check(N.lib().frei_ctx_path(self._ctx, ctypes.byref(f)))
+        v = f.value
+        return dict(fast=bool(v & 1), lds_steps=bool(v & 2), contracted=bool(v & 4),
+                    nan=bool(v & 8), paired=bool(v & 16), quad=bool(v & 32),
+                    pipe=(v >> 6) & 7, lam2=bool(v & 512), tail=bool(v & 1024),
+                    lazy_k3=bool(v & 2048), atm_tile=(v >> 12) & 7)
+
+    def set_option(self, name, value):
+        """Tuning knob of include/frei_hip.h frei_set_option (e.g. "precontract", 0)."""
+        N.check(N.lib().frei_set_option(self._ctx, name.encode(), int(value)))
+
+    def setup_timing(self):
+        """Milliseconds of the last one-time metadata build by phase (frei_setup_timing)."""
+        ms = np.zeros(5)
+        N.check(N.lib().frei_setup_timing(self._ctx, N.dptr(ms)))
+        return dict(zip(("brackets_host", "uploads", "eff_alloc", "eff_zero", "contract"),
+                        ms.tolist()))
+
+    def contract_timing(self):
+        """The last species-contraction kernel (K3, or K7 for a batched context): dict(ms = its
+        HIP-event duration, bytes = its algorithmic HBM bytes) (frei_contract_timing)."""
+        ms, nb = ctypes.c_double(0), ctypes.c_double(0)
+        N.check(N.lib().frei_contract_timing(self._ctx, ctypes.byref(ms), ctypes.byref(nb)))
+        return dict(ms=ms.value, bytes=nb.value)
+
+    def post_timing(self):
+        """HIP-event milliseconds of the kernels of the last post-processing call on this
+        context (milne_pressure, contribution, transit, emergent, BatchEngine.post)
+        (frei_post_timing)."""
+        ms = ctypes.c_double(0)
+        N.check(N.lib().frei_post_timing(self._ctx, ctypes.byref(ms)))
+        return ms.value
+
+
+class Engine(ContextBase):
     """One device context for the wavelength slice ``lam_slice`` of ``lam_um``.
 
     Parameters mirror the reference's Grid/Planet: ``p_bar`` layer pressures (bar,
@@ -236,61 +348,6 @@ class Engine:
         else:
             raise ValueError(f"unknown comm kind {kind!r}")
 
-    # ------------------------------------------------------------------ setup
-    def _set_table(self, s, tab, sl):
-        lib = N.lib()
-        p, T = _table_arrays(tab)
-        p_cgs, T = N.f64(p * BAR), N.f64(T)
-        if isinstance(tab, BinnedTable):
-            if tab.wavelength.size != self.lam_um.size:
-                raise ValueError("binned table wavelengths must match the grid")
-            N.check(lib.frei_set_table_binned(
-                self._ctx, s, tab.xsec.handle(self.device), tab.mode, N.dptr(tab.wl_bins),
-                N.dptr(tab.wavelength), tab.wavelength.size, self.lo, N.dptr(tab.temperature),
-                tab.temperature.size, N.dptr(tab.pressure), tab.pressure.size))
-            return
-        if isinstance(tab, KTable):
-            if tab.wavelength.size != self.lam_um.size:
-                raise ValueError("k-table columns (n_bins * n_g) must match the grid's columns")
-            N.check(lib.frei_set_table_kdist(
-                self._ctx, s, tab.xsec.handle(self.device), N.dptr(tab.wl_bins), tab.n_bins,
-                tab.g.size, N.dptr(tab.g), N.dptr(tab.temperature), tab.temperature.size,
-                N.dptr(tab.pressure), tab.pressure.size, self.lo))
-            return
-        if isinstance(tab, MixedKTable):
-            if tab.wavelength.size != self.lam_um.size:
-                raise ValueError("k-table columns (n_bins * n_g) must match the grid's columns")
-            if tab.device != self.device:
-                raise ValueError(f"the k-table library lives on device {tab.device}, the engine "
-                                 f"on device {self.device}")
-            N.check(lib.frei_set_table_kmix(self._ctx, s, tab.library.handle(), N.dptr(tab.x),
-                                            self.lo))
-            return
-        if isinstance(tab, SeparableTable):
-            N.check(lib.frei_set_table_separable(
-                self._ctx, s, N.dptr(N.f64(tab.base[sl])), N.dptr(N.f64(tab.fp)),
-                N.dptr(N.f64(tab.fT)), tab.lo, tab.hi, N.dptr(p_cgs), p.size, N.dptr(T), T.size))
-            return
-        vals = table_values(tab)      # transposed by name when the table carries .dims
-        if vals.ndim != 3 or vals.shape[:2] != (p.size, T.size):
-            raise ValueError("opacity table must be (pressure, temperature, wavelength)")
-        if vals.shape[2] != self.lam_um.size:
-            raise ValueError("opacity table wavelength axis must match the grid")
-        v = N.f64(vals[:, :, sl])
-        N.check(lib.frei_set_table(self._ctx, s, N.dptr(v), N.dptr(p_cgs), p.size,
-                                   N.dptr(T), T.size))
-
-    def close(self):
-        if getattr(self, "_ctx", None):
-            N.lib().frei_ctx_destroy(self._ctx)
-            self._ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # ------------------------------------------------------------------ state
     def set_fluxes(self, up=None, down=None):
         N.check(N.lib().frei_set_fluxes(self._ctx, N.dptr(None if up is None else N.f64(up)),
@@ -395,22 +452,6 @@ class Engine:
     def state_init(self, T_init):
         N.check(N.lib().frei_state_init(self._ctx, N.dptr(N.f64(T_init))))
 
-    def iterate(self, n, n_zero_crossings=-1, convergence_dT=3.0, alpha=1.0):
-        N.check(N.lib().frei_iterate(self._ctx, int(n), int(n_zero_crossings),
-                                     float(convergence_dT), float(alpha)))
-
-    def synchronize(self):
-        N.check(N.lib().frei_synchronize(self._ctx))
-
-    def timing(self, on):
-        N.check(N.lib().frei_timing_enable(self._ctx, 1 if on else 0))
-
-    def timing_read(self):
-        ms = ctypes.c_double(0)
-        n = ctypes.c_int(0)
-        N.check(N.lib().frei_timing_read(self._ctx, ctypes.byref(ms), ctypes.byref(n)))
-        return ms.value, n.value
-
     def timing_read_exchange(self):
         """(total ms, calls) of the timed rank exchanges (all-gathers) since timing(True)."""
         ms, n = ctypes.c_double(), ctypes.c_int()
@@ -457,20 +498,6 @@ class Engine:
         ``weights`` returns the intensities only."""
         return pick(*emergent_call(self, 1, T, mu, weights, dtaus, want_intensity), m=0)
 
-    def path(self):
-        """Sweep implementation the tables select: dict(fast, lds_steps, contracted, nan)."""
-        f = ctypes.c_int(0)
-        N.check(N.lib().frei_ctx_path(self._ctx, ctypes.byref(f)))
-        v = f.value
-        return dict(fast=bool(v & 1), lds_steps=bool(v & 2), contracted=bool(v & 4),
-                    nan=bool(v & 8), paired=bool(v & 16), quad=bool(v & 32),
-                    pipe=(v >> 6) & 7, lam2=bool(v & 512), tail=bool(v & 1024),
-                    lazy_k3=bool(v & 2048), atm_tile=(v >> 12) & 7)
-
-    def set_option(self, name, value):
-        """Tuning knob of include/frei_hip.h frei_set_option (e.g. "precontract", 0)."""
-        N.check(N.lib().frei_set_option(self._ctx, name.encode(), int(value)))
-
     def graph_info(self):
         """(captures, replays) of the hipGraph T-P iteration replay (frei_graph_info)."""
         cap, rep = ctypes.c_int(0), ctypes.c_int(0)
@@ -490,27 +517,6 @@ class Engine:
         n = ctypes.c_int64(0)
         N.check(N.lib().frei_chain_info(self._ctx, ctypes.byref(n)))
         return n.value
-
-    def setup_timing(self):
-        """Milliseconds of the last one-time metadata build by phase (frei_setup_timing)."""
-        ms = np.zeros(5)
-        N.check(N.lib().frei_setup_timing(self._ctx, N.dptr(ms)))
-        return dict(zip(("brackets_host", "uploads", "eff_alloc", "eff_zero", "contract"),
-                        ms.tolist()))
-
-    def contract_timing(self):
-        """The last species-contraction kernel (K3, or K7 for a batched context): dict(ms = its
-        HIP-event duration, bytes = its algorithmic HBM bytes) (frei_contract_timing)."""
-        ms, nb = ctypes.c_double(0), ctypes.c_double(0)
-        N.check(N.lib().frei_contract_timing(self._ctx, ctypes.byref(ms), ctypes.byref(nb)))
-        return dict(ms=ms.value, bytes=nb.value)
-
-    def post_timing(self):
-        """HIP-event milliseconds of the kernels of the last post-processing call
-        (milne_pressure, contribution, BatchEngine.post) on this context (frei_post_timing)."""
-        ms = ctypes.c_double(0)
-        N.check(N.lib().frei_post_timing(self._ctx, ctypes.byref(ms)))
-        return ms.value
 
     def kappa(self, T, p_bar):
         k = np.empty(self.n_lam)

@@ -636,6 +636,8 @@ int frei_klib_mix(frei_klib* lib, int n_comp, const double* x, double* out, int 
  * One composition's mixture (x[n_src][n_p][n_T]) written straight into species s of a context,
  * as frei_set_table_kdist writes a k-distribution: the context's n_lam columns are
  * [col_lo, col_lo + n_lam) of the library's n_bins * n_g; the table gets the library's nodes.
+ * The mix runs on the context's stream (the library's tables are complete when frei_klib_set and
+ * frei_klib_set_kdist return) and the call returns when the table is complete.
  */
 int frei_set_table_kmix(frei_ctx* ctx, int s, frei_klib* lib, const double* x, int64_t col_lo);
 

@@ -151,6 +151,36 @@ def test_sharded_binning_matches_whole_grid(fa, golden):
         x.release()
 
 
+@pytest.mark.parametrize("groupies", [True, False])
+def test_binned_table_with_unsorted_temperature_nodes(fa, groupies):
+    """frei_set_table_binned given the target T nodes as [2000, 1000, 1500]: kappa equals, bit
+    for bit, that of the table binned onto the ascending nodes, at two (T, p) off the nodes.
+    4 layers, 65 wavelengths (one past the 64-element row pitch), 3 x 3 nodes."""
+    rng = np.random.default_rng(66)
+    nu = np.linspace(1000.0, 20000.0, 20_001)
+    wl = (1e4 / nu)[1:][::-1]
+    lam, wl_bins, _ = O.wavelength_grid(0.5, 10, 65)
+    T_src, p_src = np.array([1000.0, 1500.0, 2000.0]), np.array([1e-4, 1e-2, 10.0])
+    xsec = (10 ** rng.uniform(-4, 2, (3, 3, wl.size))).astype(np.float32)
+    T_u = np.array([2000.0, 1000.0, 1500.0])
+    p = np.logspace(0, -3, 4)
+    x = fa.CrossSection(xsec, T_src, p_src, wl)
+    got = []
+    try:
+        for T_t in (T_u, np.sort(T_u)):
+            eng = fa.Engine(lam, p, {"x": fa.BinnedTable(x, wl_bins, lam, T_t, p_src, groupies)},
+                            mmr=np.ones((1, 4)))
+            try:
+                got.append([eng.kappa(T, pq)[0] for T, pq in ((1200.0, 0.3), (1900.0, 2e-3))])
+            finally:
+                eng.close()
+    finally:
+        x.release()
+    for a, b in zip(*got):
+        assert np.isfinite(a).sum() > 32 and np.array_equal(a, b, equal_nan=True)
+    assert not np.array_equal(got[0][0], got[0][1], equal_nan=True)
+
+
 @pytest.mark.parametrize("n_pts,n_bins", [(300_001, 3000), (100_001, 60_000)])
 def test_exact_binning_wide_and_sparse_groups_vs_oracle(fa, n_pts, n_bins):
     """The exact mode's lanes integrate the two bins of their interpolation bracket themselves:

@@ -222,8 +222,46 @@ def test_set_mix_is_in_place():
         lib.release()
 
 
+def test_update_of_a_one_atmosphere_context_remixes_species_0():
+    """A k-mix context from frei_ctx_create_batch with n_atm = 1 sweeps species 0's table:
+    frei_kmix_batch_update re-mixes that table in place, frei_get_table_batch returns the
+    library's mix of the new composition bit for bit in the library's node order (T3, unsorted),
+    and a run on it is finite.  4 layers, 13 bins x n_g 5 = 65 columns (one past the 64-element
+    row pitch), 3 x 3 nodes."""
+    rng = np.random.default_rng(165)
+    n_g, bins = 5, np.linspace(1.0, 3.0, 14)
+    P3 = np.array([10.0, 1e-1, 1e-3])
+    g, w = gauss_g(n_g)
+    Ks = np.sort(rng.lognormal(0.0, 2.0, (2, 3, 3, 13, n_g)), axis=-1)
+    klib = KLibrary({"a": Ks[0], "b": Ks[1]}, bins, g, w, T3, P3)
+    lam = np.repeat((bins[:-1] + bins[1:]) / 2, n_g)
+    qw = np.outer(np.diff(bins) * K.UM, w).ravel()
+    p = np.array([10.0, 1.0, 1e-1, 1e-3])
+    x = rng.uniform(1e-3, 1e-1, (2, 2, 3, 3))                   # (n_comp, n_src, n_T, n_p)
+    xc = klib.tables(x).x
+    want = klib.mix(x).reshape(2, 3, 3, -1)
+    assert lam.size == 65 and not same_bits(want[0], want[1])
+    lib, ctx = raw_context(lam, qw, p, 1)
+    try:
+        tab = np.empty((3, 3, 65))
+        N.check(lib.frei_set_table_kmix_batch(ctx, klib.handle(), N.dptr(N.f64(xc[:1])), 0))
+        N.check(lib.frei_get_table_batch(ctx, 0, N.dptr(tab)))
+        assert same_bits(tab, want[0])
+        N.check(lib.frei_kmix_batch_update(ctx, 0, 1, N.dptr(N.f64(xc[1:]))))
+        N.check(lib.frei_get_table_batch(ctx, 0, N.dptr(tab)))
+        assert same_bits(tab, want[1])
+        n_iter = (ctypes.c_int * 1)()
+        Tf, sp = np.empty((1, 4)), np.empty((1, 65))
+        T0 = N.f64(np.linspace(1700.0, 1100.0, 4)[None])
+        N.check(lib.frei_run_batch(ctx, N.dptr(T0), 2, 2, 3.0, 1.0, n_iter, N.dptr(Tf), N.dptr(sp)))
+        assert np.all(np.isfinite(sp)) and np.all(np.isfinite(Tf)) and n_iter[0] >= 1
+    finally:
+        lib.frei_ctx_destroy(ctx)
+        klib.release()
+
+
 # ------------------------------------------------------------------------------ 3. the oracle
-COMPS = [(0.6, 0.4), (0.2, 0.8), (1.0, 0.0), (3e-3, 0.5), (0.05, 0.01)]
+COMPS =[(0.6, 0.4), (0.2, 0.8), (1.0, 0.0), (3e-3, 0.5), (0.05, 0.01)]
 GRAVITIES = [K.G_JUPITER, 900.0, 2500.0, 4000.0, 1500.0]
 N_STEPS = 6
 

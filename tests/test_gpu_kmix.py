@@ -360,7 +360,8 @@ def test_c_level_argument_errors():
     lam = np.linspace(1.0, 2.0, 12)
     eng = Engine(lam, np.logspace(0, -3, 4), {"x": fa.OpacityTable(np.ones((2, 2, 12)), P2, T2, lam)},
                  mmr=np.ones((1, 4)))
-    fails(lib.frei_set_table_kmix(eng._ctx, 0, h, N.dptr(x), 1), "columns [1, 13) lie outside the 12")
+    fails(lib.frei_set_table_kmix(eng._ctx, 0, h, N.dptr(x), 1),
+          "frei_set_table_kmix: columns [1, 13) lie outside the 12")
     fails(lib.frei_set_table_kmix(eng._ctx, 0, h, N.dptr(x), -1), "columns [-1, 11)")
     fails(lib.frei_set_table_kmix(eng._ctx, 0, None, N.dptr(x), 0), "null argument")
     fails(lib.frei_set_table_kmix(eng._ctx, 0, h, None, 0), "null argument")

@@ -434,6 +434,38 @@ def test_nan_in_table_is_skipped_like_xarray_sum(fa):
     assert_grid_parity(spec.flux, osp, up, ou, down, od, "NaN band", floor, T=T, ref_T=oT)
 
 
+@pytest.mark.parametrize("kind", ["values", "separable"])
+def test_unsorted_temperature_nodes_store_the_same_table(fa, kind):
+    """frei_set_table and frei_set_table_separable given the T nodes as [2000, 1000, 1500]: kappa
+    equals, bit for bit, that of the same table given ascending with its rows permuted to match,
+    at two (T, p) off the nodes.  4 layers, 65 wavelengths (one past the 64-element row pitch),
+    3 x 3 nodes."""
+    rng = np.random.default_rng(65)
+    lam = np.linspace(1.0, 2.0, 65)
+    p = np.logspace(0, -3, 4)
+    p_n = np.array([1e-4, 1e-2, 10.0])
+    T_u = np.array([2000.0, 1000.0, 1500.0])
+    order = np.argsort(T_u)
+    base, fp, fT = 10 ** rng.uniform(-2, 1, 65), (p_n / 1.0) ** 0.1, (T_u / 1000.0) ** 0.5
+    if kind == "values":
+        vals = rng.lognormal(0.0, 1.0, (3, 3, 65))
+        tabs = (fa.OpacityTable(vals, p_n, T_u), fa.OpacityTable(vals[:, order], p_n, T_u[order]))
+    else:
+        tabs = (fa.SeparableTable(base, fp, fT, p_n, T_u),
+                fa.SeparableTable(base, fp, fT[order], p_n, T_u[order]))
+    got = []
+    for tab in tabs:
+        eng = fa.Engine(lam, p, {"x": tab}, mmr=np.ones((1, 4)))
+        try:
+            assert not eng.path()["nan"]
+            got.append([eng.kappa(T, pq)[0] for T, pq in ((1200.0, 0.3), (1900.0, 2e-3))])
+        finally:
+            eng.close()
+    for a, b in zip(*got):
+        assert np.all(np.isfinite(a)) and np.array_equal(a, b)
+    assert not np.array_equal(got[0][0], got[0][1])
+
+
 @pytest.mark.parametrize("mode", ["single_T", "offnode_p", "mixed_T"])
 def test_generic_sweep_path_matches_oracle(fa, mode):
     """Tables the fast kernel cannot take run the generic sweep kernel: a single-temperature
