@@ -28,6 +28,7 @@ SIGNATURES = {
     "frei_version": (ctypes.c_int, []),
     "frei_last_error": (ctypes.c_char_p, []),
     "frei_device_count": (ctypes.c_int, [_ip]),
+    "frei_live_resources": (ctypes.c_int, [ctypes.POINTER(_i64)] * 4),
     "frei_ctx_create": (ctypes.c_int, [ctypes.POINTER(_vp), ctypes.c_int, ctypes.c_int, _i64,
                                        ctypes.c_int]),
     "frei_ctx_destroy": (ctypes.c_int, [_vp]),
@@ -256,3 +257,10 @@ def device_count():
     n = ctypes.c_int(0)
     check(lib().frei_device_count(ctypes.byref(n)))
     return n.value
+
+
+def live_resources():
+    """(device buffers, pinned buffers, streams, events) this process's handles hold now."""
+    v = [_i64(0) for _ in range(4)]
+    check(lib().frei_live_resources(*[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)

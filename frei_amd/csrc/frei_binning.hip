@@ -41,20 +41,14 @@ constexpr int kGroupiesBatch = 4; // of which summed together (loads in flight)
 // Plan array `slot` of x on the device (grown when too small) holding h.
 template <typename T>
 int stage(frei_xsec* x, int slot, T** d, const std::vector<T>& h, hipStream_t st) {
-  if ((int)x->plan.size() <= slot) x->plan.resize(slot + 1, {nullptr, 0});
+  if ((int)x->plan.size() <= slot) x->plan.resize(slot + 1);
   auto& b = x->plan[slot];
-  const size_t need = std::max<size_t>(h.size(), 1) * sizeof(T);
-  if (b.second < need) {
-    if (b.first) (void)hipFree(b.first);
-    b = {nullptr, 0};
-    HIP_TRY(hipMalloc(&b.first, need));
-    b.second = need;
-  }
-  *d = static_cast<T*>(b.first);
+  TRY(b.reserve(std::max<size_t>(h.size(), 1) * sizeof(T)));
+  *d = reinterpret_cast<T*>(b.get());
   if (h.empty()) return 0;
   const size_t n = h.size() * sizeof(T);
   const size_t at = (x->pinned_used + 255) & ~size_t(255);
-  if (at + n > x->pinned_cap) return set_error("binning: plan staging buffer too small");
+  if (at + n > x->pinned.capacity()) return set_error("binning: plan staging buffer too small");
   std::memcpy(x->pinned + at, h.data(), n);
   x->pinned_used = at + n;
   HIP_TRY(hipMemcpyAsync(*d, x->pinned + at, n, hipMemcpyHostToDevice, st));
@@ -66,19 +60,7 @@ int stage(frei_xsec* x, int slot, T** d, const std::vector<T>& h, hipStream_t st
 int stage_reserve(frei_xsec* x, size_t bytes) {
   HIP_TRY(hipStreamSynchronize(x->stream));
   x->pinned_used = 0;
-  if (bytes <= x->pinned_cap) return 0;
-  if (x->pinned) (void)hipHostFree(x->pinned);
-  x->pinned = nullptr;
-  x->pinned_cap = 0;
-  HIP_TRY(hipHostMalloc((void**)&x->pinned, bytes, hipHostMallocDefault));
-  x->pinned_cap = bytes;
-  return 0;
-}
-template <typename T>
-int upload(T** d, const std::vector<T>& h, hipStream_t st) {
-  TRY(dalloc(d, h.size()));
-  if (!h.empty()) HIP_TRY(hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  return 0;
+  return x->pinned.reserve(bytes);
 }
 
 // ------------------------------------------------------------------- kernels
@@ -408,13 +390,9 @@ int bin_into(frei_xsec* x, int mode, const double* wl_bins, const double* lam, i
 
   // (the host vectors outlive every copy: the stream is synchronised before returning, on every
   // path once a plan copy may be in flight, so the next call's stage_reserve never frees or
-  // overwrites the pinned buffer under a running DMA; the timing events are destroyed there too)
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  auto cleanup = [&]() {
-    (void)hipStreamSynchronize(st);
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e), e = nullptr;
-  };
+  // overwrites the pinned buffer under a running DMA; the timing events go with the scope)
+  Event ev[2];
+  auto cleanup = [&]() { (void)hipStreamSynchronize(st); };
   // every plan array of either mode (groups <= bins), with the 256-byte alignment of each
   const size_t plan_bytes = 4096 + 16 * ((size_t)U + 1) + 8 * fan_dst.size() +
                             24 * ((size_t)n_bins + 1) + 32 * (size_t)n_out +
@@ -424,7 +402,7 @@ int bin_into(frei_xsec* x, int mode, const double* wl_bins, const double* lam, i
   if (int rc = stage(x, 0, &d_row, row_off, st)) return cleanup(), rc;
   if (x->timing)
     for (auto& e : ev)
-      if (hipEventCreate(&e) != hipSuccess) return cleanup(), set_error("hipEventCreate failed");
+      if (e.create()) return cleanup(), set_error("hipEventCreate failed");
   int rc = 0;
   if (mode == FREI_BIN_GROUPIES) {
     // bins [lam_lo, lam_lo + n_out) map 1:1 to output wavelengths
@@ -506,7 +484,7 @@ int bin_into(frei_xsec* x, int mode, const double* wl_bins, const double* lam, i
     if (!x->d_hdx) {
       std::vector<double> h(std::max<int64_t>(x->nhi - 1, 1));
       for (int64_t i = 0; i + 1 < x->nhi; ++i) h[i] = (wl[i + 1] - wl[i]) * 0.5;
-      if ((rc = upload(&x->d_hdx, h, st))) return cleanup(), rc;
+      if ((rc = upload(x->d_hdx, h, st))) return cleanup(), rc;
     }
     int64_t *d_s = nullptr, *d_e = nullptr, *d_do = nullptr;
     double *d_D = nullptr, *d_xlo = nullptr, *d_xhi = nullptr, *d_lam = nullptr;
@@ -579,10 +557,9 @@ int xsec_alloc(frei_xsec** out, int device, int n_T, int n_p, int64_t n_hi,
   x->T.assign(T_nodes, T_nodes + n_T);
   x->p.assign(p_nodes, p_nodes + n_p);
   x->wl.assign(wl_hi, wl_hi + n_hi);
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&x->d_x, (size_t)n_T * n_p * n_hi * sizeof(float)) != hipSuccess) {
-    frei_xsec_destroy(x);
+  if (hipSetDevice(device) != hipSuccess || x->stream.create() ||
+      x->d_x.alloc((size_t)n_T * n_p * n_hi)) {
+    delete x;
     return set_error("frei_xsec: device allocation failed");
   }
   *out = x;
@@ -601,7 +578,7 @@ int frei_xsec_create(frei_xsec** out, int device, const float* values, int n_T, 
   frei_xsec* x = *out;
   if (hipMemcpy(x->d_x, values, (size_t)n_T * n_p * n_hi * sizeof(float),
                 hipMemcpyHostToDevice) != hipSuccess) {
-    frei_xsec_destroy(x);
+    delete x;
     *out = nullptr;
     return set_error("frei_xsec_create: host-to-device copy failed");
   }
@@ -613,21 +590,20 @@ int frei_xsec_create_synthetic(frei_xsec** out, int device, int n_T, int n_p, in
                                const double* wl_hi, uint64_t seed) {
   TRY(xsec_alloc(out, device, n_T, n_p, n_hi, T_nodes, p_nodes, wl_hi));
   frei_xsec* x = *out;
-  double *d_T = nullptr, *d_p = nullptr, *d_wl = nullptr;
+  DevBuf<double> d_T, d_p, d_wl;
   int rc = 0;
-  if ((rc = upload(&d_T, x->T, x->stream)) || (rc = upload(&d_p, x->p, x->stream)) ||
-      (rc = upload(&d_wl, x->wl, x->stream))) {
-    dfree(d_T), dfree(d_p), dfree(d_wl);
-    frei_xsec_destroy(x);
+  if ((rc = upload(d_T, x->T, x->stream)) || (rc = upload(d_p, x->p, x->stream)) ||
+      (rc = upload(d_wl, x->wl, x->stream))) {
+    delete x;
     *out = nullptr;
     return rc;
   }
   gen_xsec_kernel<<<(unsigned)((n_hi + 255) / 256), 256, 0, x->stream>>>(x->d_x, n_T, n_p, n_hi,
-                                                                        d_T, d_p, d_wl, seed);
+                                                                        d_T.get(), d_p.get(),
+                                                                        d_wl.get(), seed);
   const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(x->stream) == hipSuccess;
-  dfree(d_T), dfree(d_p), dfree(d_wl);
   if (!ok) {
-    frei_xsec_destroy(x);
+    delete x;
     *out = nullptr;
     return set_error("frei_xsec_create_synthetic: generation failed");
   }
@@ -635,17 +611,7 @@ int frei_xsec_create_synthetic(frei_xsec** out, int device, int n_T, int n_p, in
 }
 
 int frei_xsec_destroy(frei_xsec* x) {
-  if (!x) return 0;
-  (void)hipSetDevice(x->device);
-  if (x->stream) (void)hipStreamSynchronize(x->stream);
-  dfree(x->d_x);
-  dfree(x->d_hdx);
-  dfree(x->d_scratch);
-  for (auto& b : x->plan)
-    if (b.first) (void)hipFree(b.first);
-  if (x->pinned) (void)hipHostFree(x->pinned);
-  if (x->stream) (void)hipStreamDestroy(x->stream);
-  delete x;
+  if (x) delete x;
   return 0;
 }
 
@@ -656,12 +622,7 @@ int frei_xsec_bin(frei_xsec* x, int mode, const double* wl_bins, const double* l
   if (n_T < 1 || n_p < 1) return set_error("need at least one target (T, p) node");
   HIP_TRY(hipSetDevice(x->device));
   const size_t total = (size_t)n_p * n_T * n_bins;
-  if (x->scratch_n < total) {
-    dfree(x->d_scratch);
-    x->scratch_n = 0;
-    TRY(dalloc(&x->d_scratch, total));
-    x->scratch_n = total;
-  }
+  TRY(x->d_scratch.reserve(total));
   Dest d;
   d.n_p = n_p;
   d.n_T = n_T;

@@ -26,16 +26,20 @@
 using namespace frei;
 
 struct frei_brd {
+  Stream stream;   // first: destroyed last
   int device = 0;
-  hipStream_t stream = nullptr;
   int64_t n_lam = 0;
   int n_tab = 0;
   double h = 0.0, inv_dv = 0.0;
-  double *d_u = nullptr, *d_tw = nullptr, *d_norm = nullptr, *d_tab = nullptr;
-  int32_t *d_first = nullptr, *d_count = nullptr;
+  DevBuf<double> d_u, d_tw, d_norm, d_tab;
+  DevBuf<int32_t> d_first, d_count;
   double mean_points = 0.0;   // per window: form 0 picks by it and by n_atm
-  double* d_keep = nullptr;   // [keep_atm][n_lam]: the last apply's result when it asked to keep
+  DevBuf<double> d_keep;      // [keep_atm][n_lam]: the last apply's result when it asked to keep
   int keep_atm = 0;
+  ~frei_brd() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
 };
 
 namespace {
@@ -211,12 +215,6 @@ __global__ __launch_bounds__(64) void brd_mfma_kernel(const BrdArgs a) {
   }
 }
 
-template <typename T>
-bool upload(T** d, const T* h, size_t n) {
-  return hipMalloc((void**)d, (n ? n : 1) * sizeof(T)) == hipSuccess &&
-         hipMemcpy(*d, h, n * sizeof(T), hipMemcpyHostToDevice) == hipSuccess;
-}
-
 std::string at1(const char* name, int64_t i) {
   return std::string(name) + "[" + std::to_string(i) + "]";
 }
@@ -303,12 +301,12 @@ int frei_brd_create(frei_brd** out, int device, int64_t n_lam, const double* u, 
   b->inv_dv = inv_dv;
   b->mean_points = (double)taps / (double)n_lam;
   const size_t n = (size_t)n_lam;
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking) != hipSuccess ||
-      !upload(&b->d_u, u, n) || !upload(&b->d_tw, tw, n) ||
-      !upload(&b->d_norm, norm.data(), n) || !upload(&b->d_tab, tab, (size_t)n_tab) ||
-      !upload(&b->d_first, first, n) || !upload(&b->d_count, count, n)) {
-    frei_brd_destroy(b);
+  Stream& st = b->stream;   // (the copies complete before the sources go)
+  if (hipSetDevice(device) != hipSuccess || st.create() || upload(b->d_u, u, n, st) ||
+      upload(b->d_tw, tw, n, st) || upload(b->d_norm, norm.data(), n, st) ||
+      upload(b->d_tab, tab, (size_t)n_tab, st) || upload(b->d_first, first, n, st) ||
+      upload(b->d_count, count, n, st) || hipStreamSynchronize(st) != hipSuccess) {
+    delete b;
     (void)hipGetLastError();
     return set_error("frei_brd_create: device allocation or copy failed");
   }
@@ -317,14 +315,7 @@ int frei_brd_create(frei_brd** out, int device, int64_t n_lam, const double* u, 
 }
 
 int frei_brd_destroy(frei_brd* b) {
-  if (!b) return 0;
-  (void)hipSetDevice(b->device);
-  if (b->stream) (void)hipStreamSynchronize(b->stream);
-  for (void* p : {(void*)b->d_u, (void*)b->d_tw, (void*)b->d_norm, (void*)b->d_tab,
-                  (void*)b->d_first, (void*)b->d_count, (void*)b->d_keep})
-    if (p) (void)hipFree(p);
-  if (b->stream) (void)hipStreamDestroy(b->stream);
-  delete b;
+  if (b) delete b;
   return 0;
 }
 
@@ -361,8 +352,7 @@ static int brd_apply_impl(frei_brd* b, frei_ctx* ctx, const double* x, frei_itp*
   // what an earlier call kept ends here, whether or not this call succeeds
   if (b->d_keep) {
     (void)hipStreamSynchronize(b->stream);
-    (void)hipFree(b->d_keep);
-    b->d_keep = nullptr;
+    b->d_keep.reset();
     b->keep_atm = 0;
   }
   hipStream_t st = src.stream;
@@ -407,7 +397,7 @@ static int brd_apply_impl(frei_brd* b, frei_ctx* ctx, const double* x, frei_itp*
   if (keep) call.keep(d_out);
   const int rc = call.finish();
   if (!rc && keep) {
-    b->d_keep = d_out;   // complete: finish() synchronised the stream
+    b->d_keep.adopt(d_out, A * n);   // complete: finish() synchronised the stream
     b->keep_atm = n_atm;
   }
   return rc;

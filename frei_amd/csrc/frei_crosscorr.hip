@@ -34,20 +34,24 @@
 using namespace frei;
 
 struct frei_ccf {
+  Stream stream;   // first: destroyed last
   int device = 0;
-  hipStream_t stream = nullptr;
   int64_t n_lam = 0, n_pix = 0;
   int n_vel = 0, n_exp = 0, e_pad = 0;
   int64_t p_pad = 0;          // n_pix rounded up to 16: the plan's row pitch; pads are zeros
-  int32_t* d_idx = nullptr;   // [n_vel][p_pad]
-  double* d_frac = nullptr;   // [n_vel][p_pad]
-  double* d_a = nullptr;      // [n_exp][n_pix]  (form 1: coalesced along the pixels)
-  double* d_at = nullptr;     // [p_pad][e_pad]  (form 2: an MFMA step's 16 exposures contiguous)
-  double* d_w = nullptr;      // [p_pad]
+  DevBuf<int32_t> d_idx;   // [n_vel][p_pad]
+  DevBuf<double> d_frac;   // [n_vel][p_pad]
+  DevBuf<double> d_a;      // [n_exp][n_pix]  (form 1: coalesced along the pixels)
+  DevBuf<double> d_at;     // [p_pad][e_pad]  (form 2: an MFMA step's 16 exposures contiguous)
+  DevBuf<double> d_w;      // [p_pad]
   // keep mode (frei_ccf_keep): the last successful apply's sums stay here for frei_stack_apply
   bool keep = false;
-  double *k_sfg = nullptr, *k_sg = nullptr, *k_sgg = nullptr;
+  DevBuf<double> k_sfg, k_sg, k_sgg;
   int k_atm = 0;
+  ~frei_ccf() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
 };
 
 namespace {
@@ -391,9 +395,9 @@ std::string at2(const char* name, int64_t i, int64_t k) {
 // What keep mode left ends here (the stream is idle: every apply ends synchronised).
 void drop_kept(frei_ccf* c) {
   if (c->k_sfg || c->k_sg || c->k_sgg) (void)hipSetDevice(c->device);
-  dfree(c->k_sfg);
-  dfree(c->k_sg);
-  dfree(c->k_sgg);
+  c->k_sfg.reset();
+  c->k_sg.reset();
+  c->k_sgg.reset();
   c->k_atm = 0;
 }
 
@@ -466,14 +470,10 @@ int frei_ccf_create(frei_ccf** out, int device, int64_t n_lam, int64_t n_pix, in
   c->n_exp = n_exp;
   c->e_pad = e_pad;
   const size_t na = (size_t)n_exp * (size_t)n_pix;
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&c->d_idx, np * sizeof(int32_t)) != hipSuccess ||
-      hipMalloc((void**)&c->d_frac, np * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&c->d_a, na * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&c->d_at, at.size() * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&c->d_w, w_p.size() * sizeof(double)) != hipSuccess) {
-    frei_ccf_destroy(c);
+  if (hipSetDevice(device) != hipSuccess || c->stream.create() || c->d_idx.alloc(np) ||
+      c->d_frac.alloc(np) || c->d_a.alloc(na) || c->d_at.alloc(at.size()) ||
+      c->d_w.alloc(w_p.size())) {
+    delete c;
     (void)hipGetLastError();
     return set_error("frei_ccf_create: device allocation failed");
   }
@@ -486,7 +486,7 @@ int frei_ccf_create(frei_ccf** out, int device, int64_t n_lam, int64_t n_pix, in
           hipSuccess ||
       hipMemcpy(c->d_w, w_p.data(), w_p.size() * sizeof(double), hipMemcpyHostToDevice) !=
           hipSuccess) {
-    frei_ccf_destroy(c);
+    delete c;
     (void)hipGetLastError();
     return set_error("frei_ccf_create: host-to-device copy failed");
   }
@@ -495,15 +495,7 @@ int frei_ccf_create(frei_ccf** out, int device, int64_t n_lam, int64_t n_pix, in
 }
 
 int frei_ccf_destroy(frei_ccf* c) {
-  if (!c) return 0;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  drop_kept(c);
-  for (void* p : {(void*)c->d_idx, (void*)c->d_frac, (void*)c->d_a, (void*)c->d_at,
-                  (void*)c->d_w})
-    if (p) (void)hipFree(p);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  if (c) delete c;
   return 0;
 }
 
@@ -623,9 +615,9 @@ static int ccf_apply_impl(frei_ccf* c, frei_ctx* ctx, const double* x, frei_brd*
   }
   const int rc = call.finish();
   if (!rc && c->keep) {   // complete: finish() synchronised the stream
-    c->k_sfg = d_sfg;
-    c->k_sg = d_sg;
-    c->k_sgg = d_sgg;
+    c->k_sfg.adopt(d_sfg, A * E * V);
+    c->k_sg.adopt(d_sg, A * V);
+    c->k_sgg.adopt(d_sgg, A * V);
     c->k_atm = n_atm;
   }
   return rc;

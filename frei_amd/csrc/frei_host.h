@@ -3,6 +3,8 @@
 // resolution of a spectrum's sources.  Host code only; a new post-processing call starts
 // from DeviceCall and spectrum_rows ("Host scaffold").
 #pragma once
+#include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <string>
 #include <vector>
@@ -21,30 +23,6 @@
     int _r = (expr);         \
     if (_r != 0) return _r;  \
   } while (0)
-
-// One species' high-resolution cross-section resident in HBM (include/frei_hip.h): uploaded or
-// generated by frei_binning.hip, computed from a line list by frei_lines.hip (K17), binned by K6.
-struct frei_xsec {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int nT = 0, np = 0;
-  int64_t nhi = 0;
-  std::vector<double> T, p, wl;  // K, bar, µm (ascending)
-  float* d_x = nullptr;          // [nT][np][nhi]
-  double* d_hdx = nullptr;       // 0.5 * (wl[i+1] - wl[i]), exact mode (lazy)
-  double* d_scratch = nullptr;   // output of frei_xsec_bin(out = NULL)
-  size_t scratch_n = 0;
-  bool timing = false;
-  double t_ms = 0;
-  int t_n = 0;
-  // the per-call plan arrays, kept between calls (slot k: device buffer and its capacity in
-  // bytes): no hipMalloc / hipFree per binning call
-  std::vector<std::pair<void*, size_t>> plan;
-  // pinned host staging of the plan uploads (DMA copies; pageable hipMemcpyAsync stalled the
-  // next kernel launch by milliseconds)
-  char* pinned = nullptr;
-  size_t pinned_cap = 0, pinned_used = 0;
-};
 
 namespace frei {
 
@@ -83,17 +61,155 @@ int dalloc(T** p, size_t n) {
   return 0;
 }
 
+// What is alive in this process (frei_live_resources): raised by the owning types below when
+// they acquire, lowered when they let go.
+enum LiveKind { kLiveDevice, kLivePinned, kLiveStream, kLiveEvent };
+inline std::atomic<int64_t> g_live[4];
+
+struct DeviceMem {
+  static constexpr LiveKind kind = kLiveDevice;
+  template <typename T>
+  static int get(T** p, size_t n) { return dalloc(p, n); }
+  static void put(void* p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+  static constexpr LiveKind kind = kLivePinned;
+  template <typename T>
+  static int get(T** p, size_t n) {
+    HIP_TRY(hipHostMalloc((void**)p, (n ? n : 1) * sizeof(T), hipHostMallocDefault));
+    return 0;
+  }
+  static void put(void* p) { (void)hipHostFree(p); }
+};
+
+// Owns n elements of device (DevBuf) or pinned host (PinnedBuf) memory; converts to T* wherever
+// a raw pointer is read.  reserve() and reset() never synchronise: where queued work may still
+// read the old buffer, the caller synchronises its stream first.
+template <typename T, typename Mem>
+class Buf {
+ public:
+  Buf() = default;
+  Buf(Buf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
+  Buf& operator=(Buf&& o) noexcept {
+    if (this != &o) adopt_counted(o.p_, o.cap_), o.p_ = nullptr, o.cap_ = 0;
+    return *this;
+  }
+  ~Buf() { reset(); }
+
+  operator T*() const { return p_; }
+  T* get() const { return p_; }
+  size_t capacity() const { return cap_; }
+
+  // Releases what it holds and allocates exactly n elements (one for n == 0).
+  int alloc(size_t n) {
+    reset();
+    if (int rc = Mem::get(&p_, n)) {
+      p_ = nullptr;
+      (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
+      return rc;
+    }
+    cap_ = n;
+    ++g_live[Mem::kind];
+    return 0;
+  }
+  // Grow-only; contents are never preserved, and a failure leaves the capacity at zero.
+  int reserve(size_t n) { return p_ && n <= cap_ ? 0 : alloc(n); }
+  void reset() {
+    if (p_) Mem::put((void*)p_), --g_live[Mem::kind];
+    p_ = nullptr, cap_ = 0;
+  }
+  T* release() {
+    T* p = p_;
+    if (p) --g_live[Mem::kind];
+    p_ = nullptr, cap_ = 0;
+    return p;
+  }
+  // Takes n elements at p obtained elsewhere (freed like its own).
+  void adopt(T* p, size_t n) {
+    if (p) ++g_live[Mem::kind];
+    adopt_counted(p, n);
+  }
+
+ private:
+  void adopt_counted(T* p, size_t n) {
+    reset();
+    p_ = p, cap_ = p ? n : 0;
+  }
+  T* p_ = nullptr;
+  size_t cap_ = 0;
+};
 template <typename T>
-void dfree(T*& p) {
-  if (p) (void)hipFree((void*)p);
-  p = nullptr;
-}
+using DevBuf = Buf<T, DeviceMem>;
+template <typename T>
+using PinnedBuf = Buf<T, PinnedMem>;
+
+class Stream {
+ public:
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  Stream& operator=(const Stream&) = delete;
+  ~Stream() {
+    if (s_) (void)hipStreamDestroy(s_), --g_live[kLiveStream];
+  }
+  operator hipStream_t() const { return s_; }
+  int create() {   // once; non-blocking
+    HIP_TRY(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
+    ++g_live[kLiveStream];
+    return 0;
+  }
+
+ private:
+  hipStream_t s_ = nullptr;
+};
+
+class Event {
+ public:
+  Event() = default;
+  Event(Event&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+  Event& operator=(Event&& o) noexcept {
+    if (this != &o) reset(), e_ = o.e_, o.e_ = nullptr;
+    return *this;
+  }
+  ~Event() { reset(); }
+  operator hipEvent_t() const { return e_; }
+  int create(unsigned flags = hipEventDefault) {
+    reset();
+    HIP_TRY(hipEventCreateWithFlags(&e_, flags));
+    ++g_live[kLiveEvent];
+    return 0;
+  }
+  void reset() {
+    if (e_) (void)hipEventDestroy(e_), --g_live[kLiveEvent];
+    e_ = nullptr;
+  }
+
+ private:
+  hipEvent_t e_ = nullptr;
+};
+
+// A device pointer parameter whose T is deduced from the host pointer beside it, so that a
+// DevBuf<T> converts where it is passed.
+template <typename T>
+struct NoDeduce { using type = T; };
+template <typename T>
+using DevPtr = typename NoDeduce<T>::type*;
 
 // Queued on st: the source must outlive the stream's next synchronisation.
 template <typename T>
-int h2d(T* d, const T* h, size_t n, hipStream_t st) {
+int h2d(DevPtr<T> d, const T* h, size_t n, hipStream_t st) {
   HIP_TRY(hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, st));
   return 0;
+}
+
+// d becomes n elements holding h (queued on st, like h2d).
+template <typename T>
+int upload(DevBuf<T>& d, const T* h, size_t n, hipStream_t st) {
+  TRY(d.alloc(n));
+  return n ? h2d(d.get(), h, n, st) : 0;
+}
+template <typename T>
+int upload(DevBuf<T>& d, const std::vector<T>& h, hipStream_t st) {
+  return upload(d, h.data(), h.size(), st);
 }
 
 // One post-processing call on one stream: owns what the call allocates, keeps the first error
@@ -123,10 +239,10 @@ class DeviceCall {
 
   template <typename T>
   T* alloc(size_t n) {
-    T* p = nullptr;
-    if (rc_ || (rc_ = dalloc(&p, n))) return nullptr;
-    owned_.push_back(p);
-    return p;
+    if (rc_) return nullptr;
+    owned_.emplace_back();
+    rc_ = owned_.back().alloc(n * sizeof(T));
+    return reinterpret_cast<T*>(owned_.back().get());
   }
   template <typename T>
   T* upload(const T* host, size_t n) {
@@ -136,11 +252,11 @@ class DeviceCall {
   }
   // Into a buffer the call does not own.
   template <typename T>
-  void copy_in(T* dev, const T* host, size_t n) {
+  void copy_in(DevPtr<T> dev, const T* host, size_t n) {
     if (!rc_) rc_ = h2d(dev, host, n, st_);
   }
   template <typename T>
-  void download(T* host, const T* dev, size_t n) {
+  void download(T* host, DevPtr<const T> dev, size_t n) {
     if (!rc_ && host &&
         hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, st_) != hipSuccess)
       rc_ = set_error(what_ + " copy failed");
@@ -154,8 +270,7 @@ class DeviceCall {
     if (rc_ || !ms) return;
     ms_ = ms;
     *ms_ = 0.0;
-    if (hipEventCreate(&ev_[0]) != hipSuccess || hipEventCreate(&ev_[1]) != hipSuccess ||
-        hipEventRecord(ev_[0], st_) != hipSuccess)
+    if (ev_[0].create() || ev_[1].create() || hipEventRecord(ev_[0], st_) != hipSuccess)
       rc_ = set_error(what_ + ": timing event failed");
   }
   void end() {
@@ -167,8 +282,8 @@ class DeviceCall {
       rc_ = set_error(what_ + ": timing event failed");
   }
 
-  // p (from alloc; null is ignored) outlives a successful finish() as the caller's; a failed
-  // one frees it.  Any number of buffers may be kept.
+  // p (from alloc; null is ignored) outlives a successful finish() as the caller's, who adopts
+  // it into a DevBuf; a failed one frees it.  Any number of buffers may be kept.
   void keep(void* p) {
     if (p) kept_.push_back(p);
   }
@@ -181,10 +296,11 @@ class DeviceCall {
     if (hipStreamSynchronize(st_) != hipSuccess && !rc_) rc_ = set_error(what_ + " kernel failed");
     float ms = 0.f;
     if (!rc_ && ms_ && hipEventElapsedTime(&ms, ev_[0], ev_[1]) == hipSuccess) *ms_ = ms;
-    for (hipEvent_t e : ev_)
-      if (e) (void)hipEventDestroy(e);
-    for (void* p : owned_)
-      if (rc_ || std::find(kept_.begin(), kept_.end(), p) == kept_.end()) (void)hipFree(p);
+    for (Event& e : ev_) e.reset();
+    for (DevBuf<char>& b : owned_)
+      if (!rc_ && std::find(kept_.begin(), kept_.end(), (void*)b.get()) != kept_.end())
+        (void)b.release();
+    owned_.clear();
     if (rc_) (void)hipGetLastError();   // a failed allocation must not fail the next call's checks
     return rc_;
   }
@@ -195,8 +311,8 @@ class DeviceCall {
   int rc_ = 0;
   bool done_ = false;
   double* ms_ = nullptr;
-  hipEvent_t ev_[2] = {nullptr, nullptr};
-  std::vector<void*> owned_;
+  Event ev_[2];
+  std::vector<DevBuf<char>> owned_;
   std::vector<void*> kept_;
 };
 
@@ -285,3 +401,30 @@ inline int check_select(const std::string& name, const int32_t* select, int n_at
 }
 
 }  // namespace frei
+
+// One species' high-resolution cross-section resident in HBM (include/frei_hip.h): uploaded or
+// generated by frei_binning.hip, computed from a line list by frei_lines.hip (K17), binned by K6.
+struct frei_xsec {
+  frei::Stream stream;           // first: destroyed after everything queued on it is freed
+  int device = 0;
+  int nT = 0, np = 0;
+  int64_t nhi = 0;
+  std::vector<double> T, p, wl;  // K, bar, µm (ascending)
+  frei::DevBuf<float> d_x;          // [nT][np][nhi]
+  frei::DevBuf<double> d_hdx;       // 0.5 * (wl[i+1] - wl[i]), exact mode (lazy)
+  frei::DevBuf<double> d_scratch;   // output of frei_xsec_bin(out = NULL), grow-only
+  bool timing = false;
+  double t_ms = 0;
+  int t_n = 0;
+  // the per-call plan arrays, kept between calls (slot k, in bytes, grow-only): no allocation
+  // per binning call
+  std::vector<frei::DevBuf<char>> plan;
+  // pinned host staging of the plan uploads (DMA copies; pageable hipMemcpyAsync stalled the
+  // next kernel launch by milliseconds)
+  frei::PinnedBuf<char> pinned;
+  size_t pinned_used = 0;
+  ~frei_xsec() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
+};

@@ -26,19 +26,23 @@
 using namespace frei;
 
 struct frei_itp {
+  Stream stream;   // first: destroyed last; created by the first frei_itp_set_nodes
   int device = 0;
-  hipStream_t stream = nullptr;   // created by the first frei_itp_set_nodes
   int64_t n_lam = 0, pitch = 0;
   int n_node = 0;
   int tile = 0;                   // form 2's tile width, 0 where the library is too tall for it
-  double* d_x = nullptr;          // [n_node][pitch]
+  DevBuf<double> d_x;             // [n_node][pitch]
   bool have_nodes = false;
   // The result buffer, reused from call to call and grown when a call needs more (a sampler
-  // step of thousands of queries then allocates and frees no gigabytes): [out_cap] doubles, of
-  // which the first keep_q * n_lam are the last apply's result when it asked to keep (else 0).
-  double* d_out = nullptr;
-  size_t out_cap = 0;
+  // step of thousands of queries then allocates and frees no gigabytes), of which the first
+  // keep_q * n_lam doubles are the last apply's result when it asked to keep (else 0).
+  DevBuf<double> d_out;
   int keep_q = 0;
+  ~frei_itp() {
+    if (!stream) return;   // no device was touched
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+  }
 };
 
 namespace {
@@ -210,15 +214,7 @@ int frei_itp_create(frei_itp** out, int device, int64_t n_lam, int n_node) {
 }
 
 int frei_itp_destroy(frei_itp* p) {
-  if (!p) return 0;
-  if (p->stream || p->d_x || p->d_out) {
-    (void)hipSetDevice(p->device);
-    if (p->stream) (void)hipStreamSynchronize(p->stream);
-    dfree(p->d_x);
-    dfree(p->d_out);
-    if (p->stream) (void)hipStreamDestroy(p->stream);
-  }
-  delete p;
+  if (p) delete p;
   return 0;
 }
 
@@ -229,15 +225,15 @@ int frei_itp_set_nodes(frei_itp* p, frei_ctx* ctx, frei_brd* brd, const double* 
   TRY(spectrum_rows(x, ctx, brd, nullptr, nullptr, p->n_node, p->n_lam, p->device, nullptr,
                     "interpolator", "frei_itp_set_nodes", &src));
   HIP_TRY(hipSetDevice(p->device));
-  if (!p->stream) HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  if (!p->stream) TRY(p->stream.create());
   // the library and whatever was kept end here, whether or not this call succeeds
   p->keep_q = 0;
   p->have_nodes = false;
   HIP_TRY(hipStreamSynchronize(p->stream));
   const size_t rows = (size_t)p->n_node, pitch = (size_t)p->pitch * sizeof(double);
-  if (!p->d_x) TRY(dalloc(&p->d_x, rows * (size_t)p->pitch));
+  if (!p->d_x) TRY(p->d_x.alloc(rows * (size_t)p->pitch));
   // a context's rows are copied on its stream, behind the work that writes them
-  hipStream_t st = src.stream ? src.stream : p->stream;
+  hipStream_t st = src.stream ? src.stream : (hipStream_t)p->stream;
   HIP_TRY(hipMemsetAsync(p->d_x, 0, rows * pitch, st));
   if (x)
     HIP_TRY(hipMemcpy2DAsync(p->d_x, pitch, x, (size_t)p->n_lam * sizeof(double),
@@ -289,12 +285,7 @@ int frei_itp_apply(frei_itp* p, int n_query, int n_corner, const int32_t* idx, c
   hipStream_t st = p->stream;
   const size_t Q = (size_t)n_query, n = (size_t)p->n_lam, C = (size_t)n_corner;
   DeviceCall call(st, "interpolation");
-  if (Q * n > p->out_cap) {   // every earlier call has finished: its stream was synchronised
-    dfree(p->d_out);
-    p->out_cap = 0;
-    call.check(dalloc(&p->d_out, Q * n));
-    if (call.ok()) p->out_cap = Q * n;
-  }
+  call.check(p->d_out.reserve(Q * n));   // every earlier call has finished (synchronised)
   ItpArgs a;
   a.x = p->d_x;
   a.pitch = p->pitch;

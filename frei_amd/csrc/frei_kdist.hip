@@ -287,12 +287,7 @@ int kdist_into(frei_xsec* x, const double* wl_bins, int64_t n_bins, int n_g, con
 
   // ---- device
   if (!d_out) {
-    if (x->scratch_n < scratch_n) {
-      dfree(x->d_scratch);
-      x->scratch_n = 0;
-      TRY(dalloc(&x->d_scratch, scratch_n));
-      x->scratch_n = scratch_n;
-    }
+    TRY(x->d_scratch.reserve(scratch_n));
     d_out = x->d_scratch;
   }
   double ms = 0.0;
@@ -422,7 +417,7 @@ int frei_xsec_mix(frei_xsec** out, int n_src, frei_xsec* const* src, const doubl
     rc = call.finish();
   }
   if (rc) {
-    frei_xsec_destroy(x);
+    delete x;
     return rc;
   }
   *out = x;

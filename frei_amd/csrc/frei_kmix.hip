@@ -38,19 +38,22 @@
 using namespace frei;
 
 struct frei_klib {
+  Stream stream;   // first: destroyed last
   int device = 0;
-  hipStream_t stream = nullptr;
   int n_src = 0, n_p = 0, n_T = 0, n_g = 0;
   int64_t n_bins = 0;
   std::vector<double> wl_bins, g, w, p, T;
   std::vector<uint64_t> W;   // [n_g] fixed-point weights
   std::vector<uint64_t> E;   // [n_g + 1] interval bounds in units of Wt^2
   std::vector<char> set;     // [n_src] slot holds a table
-  double* d_k = nullptr;     // [n_src][n_p][n_T][n_bins][n_g]
-  uint64_t* d_W = nullptr;
-  uint64_t* d_E = nullptr;
-  double* d_out = nullptr;   // the result of frei_klib_mix
-  size_t out_cap = 0;
+  DevBuf<double> d_k;        // [n_src][n_p][n_T][n_bins][n_g]
+  DevBuf<uint64_t> d_W;
+  DevBuf<uint64_t> d_E;
+  DevBuf<double> d_out;      // the result of frei_klib_mix (grow-only)
+  ~frei_klib() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
 };
 
 namespace {
@@ -484,13 +487,13 @@ int frei_klib_create(frei_klib** out, int device, int n_src, int n_p, int n_T, i
   h->E = E;
   h->set.assign(n_src, 0);
   const size_t total = (size_t)n_src * n_p * n_T * (size_t)n_bins * n_g;
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      dalloc(&h->d_k, total) || dalloc(&h->d_W, W.size()) || dalloc(&h->d_E, E.size()) ||
+  if (h->stream.create() || h->d_k.alloc(total) || h->d_W.alloc(W.size()) ||
+      h->d_E.alloc(E.size()) ||
       hipMemcpy(h->d_W, W.data(), W.size() * sizeof(uint64_t), hipMemcpyHostToDevice) !=
           hipSuccess ||
       hipMemcpy(h->d_E, E.data(), E.size() * sizeof(uint64_t), hipMemcpyHostToDevice) !=
           hipSuccess) {
-    frei_klib_destroy(h);
+    delete h;
     (void)hipGetLastError();
     return set_error(me + "device allocation failed");
   }
@@ -499,17 +502,7 @@ int frei_klib_create(frei_klib** out, int device, int n_src, int n_p, int n_T, i
 }
 
 int frei_klib_destroy(frei_klib* lib) {
-  if (!lib) return 0;
-  (void)hipSetDevice(lib->device);
-  if (lib->stream) {
-    (void)hipStreamSynchronize(lib->stream);
-    (void)hipStreamDestroy(lib->stream);
-  }
-  dfree(lib->d_k);
-  dfree(lib->d_W);
-  dfree(lib->d_E);
-  dfree(lib->d_out);
-  delete lib;
+  if (lib) delete lib;
   return 0;
 }
 
@@ -556,12 +549,7 @@ int frei_klib_mix(frei_klib* lib, int n_comp, const double* x, double* out, int 
   TRY(choose_form(me, lib, &form));
   const size_t rows = (size_t)n_comp * lib->n_p * lib->n_T, total = rows * (size_t)n_col;
   HIP_TRY(hipSetDevice(lib->device));
-  if (lib->out_cap < total) {
-    dfree(lib->d_out);
-    lib->out_cap = 0;
-    TRY(dalloc(&lib->d_out, total));
-    lib->out_cap = total;
-  }
+  TRY(lib->d_out.reserve(total));
   std::vector<int64_t> dst(rows);
   for (size_t r = 0; r < rows; ++r) dst[r] = (int64_t)r * n_col;
   const std::vector<KmixRow> list = all_rows(n_comp, lib->n_p * lib->n_T, dst.data());

@@ -343,11 +343,10 @@ int frei_xsec_create_lines(frei_xsec** out, int device, int64_t n_line, const do
   x->T.assign(T_nodes, T_nodes + n_T);
   x->p.assign(p_nodes, p_nodes + n_p);
   x->wl.assign(wl_hi, wl_hi + n_hi);
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&x->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&x->d_x, (size_t)n_T * n_p * n_hi * sizeof(float)) != hipSuccess) {
+  if (hipSetDevice(device) != hipSuccess || x->stream.create() ||
+      x->d_x.alloc((size_t)n_T * n_p * n_hi)) {
     (void)hipGetLastError();
-    frei_xsec_destroy(x);
+    delete x;
     return set_error(std::string(kWhat) + "device allocation failed");
   }
   int rc = 0;
@@ -392,7 +391,7 @@ int frei_xsec_create_lines(frei_xsec** out, int device, int64_t n_line, const do
     rc = call.finish();
   }
   if (rc) {
-    frei_xsec_destroy(x);
+    delete x;
     return rc;
   }
   *out = x;

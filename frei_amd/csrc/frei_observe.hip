@@ -26,11 +26,15 @@
 using namespace frei;
 
 struct frei_obs {
+  Stream stream;   // first: destroyed last
   int device = 0;
-  hipStream_t stream = nullptr;
   int64_t n_lam = 0, K = 0, nnz = 0;
-  int64_t* d_plan = nullptr;   // first[K], count[K], off[K]
-  double* d_w = nullptr;       // [nnz]
+  DevBuf<int64_t> d_plan;   // first[K], count[K], off[K]
+  DevBuf<double> d_w;       // [nnz]
+  ~frei_obs() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
 };
 
 namespace {
@@ -247,11 +251,9 @@ int frei_obs_create(frei_obs** out, int device, int64_t n_lam, int64_t n_chan,
   o->n_lam = n_lam;
   o->K = n_chan;
   o->nnz = nnz;
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&o->d_plan, plan.size() * sizeof(int64_t)) != hipSuccess ||
-      hipMalloc((void**)&o->d_w, (size_t)nnz * sizeof(double)) != hipSuccess) {
-    frei_obs_destroy(o);
+  if (hipSetDevice(device) != hipSuccess || o->stream.create() || o->d_plan.alloc(plan.size()) ||
+      o->d_w.alloc((size_t)nnz)) {
+    delete o;
     (void)hipGetLastError();
     return set_error("frei_obs_create: device allocation failed");
   }
@@ -259,7 +261,7 @@ int frei_obs_create(frei_obs** out, int device, int64_t n_lam, int64_t n_chan,
           hipSuccess ||
       hipMemcpy(o->d_w, weights, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice) !=
           hipSuccess) {
-    frei_obs_destroy(o);
+    delete o;
     (void)hipGetLastError();
     return set_error("frei_obs_create: host-to-device copy failed");
   }
@@ -268,13 +270,7 @@ int frei_obs_create(frei_obs** out, int device, int64_t n_lam, int64_t n_chan,
 }
 
 int frei_obs_destroy(frei_obs* o) {
-  if (!o) return 0;
-  (void)hipSetDevice(o->device);
-  if (o->stream) (void)hipStreamSynchronize(o->stream);
-  if (o->d_plan) (void)hipFree(o->d_plan);
-  if (o->d_w) (void)hipFree(o->d_w);
-  if (o->stream) (void)hipStreamDestroy(o->stream);
-  delete o;
+  if (o) delete o;
   return 0;
 }
 

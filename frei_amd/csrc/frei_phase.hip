@@ -138,14 +138,17 @@ struct frei_phs {
   std::vector<PhsVisit> visits;
   std::vector<int32_t> tile_off;      // [n_tile + 1]
   bool resident = false;
-  PhsVisit* d_visits = nullptr;
-  int32_t* d_tile_off = nullptr;
-  // The result buffer, reused from call to call and grown when a call needs more: [out_cap]
-  // doubles, of which the first n_phase * keep_lam are the last apply's result when it asked to
-  // keep (keep_lam = 0: nothing kept).
-  double* d_out = nullptr;
-  size_t out_cap = 0;
+  DevBuf<PhsVisit> d_visits;
+  DevBuf<int32_t> d_tile_off;
+  // The result buffer, reused from call to call and grown when a call needs more, of which the
+  // first n_phase * keep_lam doubles are the last apply's result when it asked to keep
+  // (keep_lam = 0: nothing kept).
+  DevBuf<double> d_out;
   int64_t keep_lam = 0;
+  // (no stream of its own: it works on the context's, and every apply ends synchronised)
+  ~frei_phs() {
+    if (d_visits || d_tile_off || d_out) (void)hipSetDevice(device);
+  }
 };
 
 namespace {
@@ -154,8 +157,8 @@ namespace {
 int make_resident(frei_phs* p) {
   if (p->resident) return 0;
   const size_t nv = p->visits.size();
-  if (!p->d_visits) TRY(dalloc(&p->d_visits, nv));
-  if (!p->d_tile_off) TRY(dalloc(&p->d_tile_off, p->tile_off.size()));
+  if (!p->d_visits) TRY(p->d_visits.alloc(nv));
+  if (!p->d_tile_off) TRY(p->d_tile_off.alloc(p->tile_off.size()));
   if (nv)
     HIP_TRY(hipMemcpy(p->d_visits, p->visits.data(), nv * sizeof(PhsVisit),
                       hipMemcpyHostToDevice));
@@ -241,14 +244,7 @@ int frei_phs_create(frei_phs** out, int device, int n_cell, int n_phase, const i
 }
 
 int frei_phs_destroy(frei_phs* p) {
-  if (!p) return 0;
-  if (p->d_visits || p->d_tile_off || p->d_out) {
-    (void)hipSetDevice(p->device);
-    dfree(p->d_visits);
-    dfree(p->d_tile_off);
-    dfree(p->d_out);
-  }
-  delete p;
+  if (p) delete p;
   return 0;
 }
 
@@ -296,12 +292,7 @@ int frei_phs_apply(frei_phs* p, frei_ctx* ctx, const double* dtaus, const double
   TRY(make_resident(p));
   const size_t P = (size_t)p->n_phase;
   DeviceCall call(cc.stream, "phase curve");
-  if (P * n > p->out_cap) {   // every earlier call has finished: its stream was synchronised
-    dfree(p->d_out);
-    p->out_cap = 0;
-    call.check(dalloc(&p->d_out, P * n));
-    if (call.ok()) p->out_cap = P * n;
-  }
+  call.check(p->d_out.reserve(P * n));   // every earlier call has finished (synchronised)
   const double* u_dt = call.upload(dtaus, A * per);
   PhsArgs a;
   a.dtaus = u_dt ? u_dt : cc.dtaus;

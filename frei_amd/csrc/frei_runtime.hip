@@ -73,7 +73,7 @@ Rccl* rccl() {
 constexpr int kNcclFloat64 = 8;
 
 struct Species {
-  double* d_tab = nullptr;
+  DevBuf<double> d_tab;
   int n_p = 0, n_T = 0;
   int has_nan = 1;     // set by a device scan after upload/generation
   int64_t stride = 0;  // row pitch in elements (n_lam rounded up to 64, zero padded)
@@ -89,22 +89,23 @@ int64_t node_offset(const Species& q, int kp, int kt) {
 }  // namespace
 
 struct frei_ctx {
+  Stream stream;   // first: destroyed last, after every buffer and event
   int device = 0;
-  hipStream_t stream = nullptr;
   int nL = 0, S = 0;
   int64_t nlam = 0;
   int nblocks = 0;
   // grid
-  double *d_c1 = nullptr, *d_hcl = nullptr, *d_sig = nullptr, *d_ftoa = nullptr,
-         *d_wtr = nullptr, *d_p = nullptr, *d_lnp = nullptr;
+  DevBuf<double> d_c1, d_hcl, d_sig, d_ftoa, d_wtr, d_p, d_lnp;
   std::vector<double> p;
   double p_top2 = 0, g = 0, m_bar = 0;
   bool grid_set = false;
   // state
-  double *d_Fu = nullptr, *d_Fd = nullptr, *d_T = nullptr, *d_dT = nullptr,
-         *d_dtaus = nullptr, *d_bol = nullptr;
+  DevBuf<double> d_Fu, d_Fd, d_dT, d_dtaus, d_bol;
   // the fused reduce + update writes the new temperatures into the other buffer and the two
-  // swap (d_T is always the current one); d_done: its arrival counter
+  // swap (d_T is always the current one); d_done: its arrival counter.  The three temperature
+  // buffers are owned by T_buf; d_T, d_T_alt, d_T3 and d_T_home are views that rotate over them
+  DevBuf<double> T_buf[3];
+  double* d_T = nullptr;
   double* d_T_alt = nullptr;
   double* d_T3 = nullptr;               // third temperature buffer (chained launches)
   double* d_T_home = nullptr;           // the buffer d_T names after a host upload
@@ -113,10 +114,10 @@ struct frei_ctx {
   int chain = 1;                        // FREI_CHAIN
   bool has_pend = false;                // an update deferred to the next launch
   UpdateArgs pend{};
-  unsigned long long* d_epoch = nullptr;  // [n_layers] the chained update's per-layer granules
+  DevBuf<unsigned long long> d_epoch;     // [n_layers] the chained update's per-layer granules
   unsigned long long chain_seq = 0;
-  int* d_chain_err = nullptr;           // a chained sweep block's wait gave up
-  unsigned* d_done = nullptr;
+  DevBuf<int> d_chain_err;              // a chained sweep block's wait gave up
+  DevBuf<unsigned> d_done;
   int fused_update = 1;                 // FREI_FUSED_UPDATE=0: separate reduce and update kernels
   // T-P iterations replayed from a captured hipGraph (frei_iterate / frei_run, timing off,
   // single rank): g_key holds the hashes of one iteration's kernel arguments; any change
@@ -134,7 +135,7 @@ struct frei_ctx {
   // published its steps (launch_sweep_pipe_tail).  Two partial-sum buffers used alternately:
   // a launch publishes into one and its update workgroups put the other back to kPoisonT.
   int tail = 1;                         // FREI_TAIL: 1 when it applies, 0 off
-  double* d_tpart = nullptr;            // [2][tpart_n]
+  DevBuf<double> d_tpart;               // [2][tpart_n]
   int64_t tpart_n = 0;
   int tpart_parity = 0;
   bool tpart_fill = true;               // both buffers must be (re)filled with kPoisonT
@@ -148,26 +149,26 @@ struct frei_ctx {
   bool meta_dirty = true;
   bool mmr_dirty = false;               // only the mixing ratios changed (per-sweep provider)
   int fast = 1;
-  SpecMeta* d_smeta = nullptr;
-  PMeta* d_pmeta = nullptr;
-  double* d_tnodes = nullptr;
-  int32_t* d_tperm = nullptr;
-  double* d_mmr = nullptr;
+  DevBuf<SpecMeta> d_smeta;
+  DevBuf<PMeta> d_pmeta;
+  DevBuf<double> d_tnodes;
+  DevBuf<int32_t> d_tperm;
+  DevBuf<double> d_mmr;
   std::vector<SpecMeta> smeta;
   std::vector<PMeta> pmeta;
   std::vector<double> tnodes;
   std::vector<int32_t> tperm;
   // sweep scratch
-  StepP* d_steps = nullptr;
-  TermP* d_terms = nullptr;
-  FastStep* d_fsteps = nullptr;
-  FastStepS* d_ssteps = nullptr;
+  DevBuf<StepP> d_steps;
+  DevBuf<TermP> d_terms;
+  DevBuf<FastStep> d_fsteps;
+  DevBuf<FastStepS> d_ssteps;
   int shared = 0;   // fast path with one bracket for all species (identical nodes)
   // Species-contracted table (K3): with shared nodes, no NaN and fixed per-layer mmr the
   // sweep reads eff[p][t][:] = sum_s mmr_s(l) tab_s[p][t][:] (2 rows per layer, not 2 S).
   // FREI_PRECONTRACT=0 keeps the per-species sum inside the sweep.
   int eff = 0, eff_mode = -1;
-  double* d_eff = nullptr;
+  DevBuf<double> d_eff;   // grow-only
   // Lazy K3 (FREI_LAZY_K3, round 6): with the two-wavelength sweep, the setup contracts no row;
   // a sweep contracts the rows its records mask as missing (the lane's own wavelengths), and the
   // update after it marks them (d_kvalid).  A run touches a fraction of the table's T nodes (C3
@@ -176,43 +177,42 @@ struct frei_ctx {
   int lazy_k3 = 1;
   bool lazy_on = false;
   bool eff_complete = true;
-  int32_t* d_kvalid = nullptr;
-  size_t eff_cap = 0;
-  SpecMeta* d_smeta_eff = nullptr;
-  double* d_ones = nullptr;
-  int32_t* d_prow = nullptr;
+  DevBuf<int32_t> d_kvalid;
+  DevBuf<SpecMeta> d_smeta_eff;
+  DevBuf<double> d_ones;
+  DevBuf<int32_t> d_prow;
   bool dtaus_valid = false;  // d_dtaus holds the last frei_run's final-emit dtaus
   // Batched atmospheres (frei_ctx_create_batch): n_atm atmospheres share the wavelength and
   // pressure grids and the opacity tables; every per-atmosphere buffer is n_atm blocks.
   int n_atm = 1;
-  double* d_g = nullptr;      // [n_atm] gravity (batched)
+  DevBuf<double> d_g;         // [n_atm] gravity (batched)
   size_t eff_stride = 0;      // elements per atmosphere of d_eff
-  int* h_conv = nullptr;      // pinned [2][n_atm] convergence flags (frei_run_batch)
+  PinnedBuf<int> h_conv;      // pinned [2][n_atm] convergence flags (frei_run_batch)
   bool batch_api = false;     // created through frei_ctx_create_batch (n_atm may be 1)
   // d_dtaus holds every atmosphere's final-emit dtaus [n_atm][nL][nlam] of the last
   // frei_run_batch_ex(keep_dtaus) and d_T / d_Fu are still that run's (frei_post_batch)
   bool dtaus_batch_valid = false;
   double post_ms = 0.0;       // HIP-event time of the last post-processing call's kernels
-  double *d_part = nullptr, *d_Fb = nullptr, *d_Fb_all = nullptr;
+  DevBuf<double> d_part, d_Fb, d_Fb_all;
   // T-P loop state
-  int* d_conv = nullptr;
-  int* d_iter = nullptr;
-  double *d_Tb = nullptr, *d_Ta = nullptr, *d_hist = nullptr;
+  DevBuf<int> d_conv;
+  DevBuf<int> d_iter;
+  DevBuf<double> d_Tb, d_Ta, d_hist;
   int hist_cap = 0;
-  int32_t *d_flips = nullptr, *d_prev = nullptr, *d_ndiff = nullptr;
-  int* h_flag = nullptr;  // pinned [2]
-  int* h_err = nullptr;   // pinned [2]: the chained-poll and P2P error flags (check_comm)
+  DevBuf<int32_t> d_flips, d_prev, d_ndiff;
+  PinnedBuf<int> h_flag;  // pinned [2]
+  PinnedBuf<int> h_err;   // pinned [2]: the chained-poll and P2P error flags (check_comm)
   // pinned staging of the per-sweep host round trip of a chemistry provider stepping the loop
   // (frei_get_temperatures, frei_sweep's dT / bolometric sums, frei_set_mmr's upload): one
   // stream synchronisation per read, none for the upload (pageable copies add their own)
-  double* h_T = nullptr;     // [n_layers * n_atm]
-  double* h_dT = nullptr;    // [n_layers]
-  double* h_bol = nullptr;   // [n_layers * 4]
-  double* h_mmr = nullptr;   // [n_species * n_layers * n_atm]
-  hipEvent_t mmr_ev = nullptr;   // the last upload from h_mmr
+  PinnedBuf<double> h_T;     // [n_layers * n_atm]
+  PinnedBuf<double> h_dT;    // [n_layers]
+  PinnedBuf<double> h_bol;   // [n_layers * 4]
+  PinnedBuf<double> h_mmr;   // [n_species * n_layers * n_atm]
+  Event mmr_ev;              // the last upload from h_mmr
   bool mmr_ev_set = false;
   int64_t chain_checked = 0;   // n_chained at the last check_comm
-  hipEvent_t flag_ev[2] = {nullptr, nullptr};
+  Event flag_ev[2];
   // comm
   void* comm = nullptr;
   int nranks = 1, rank = 0;
@@ -263,13 +263,13 @@ struct frei_ctx {
   bool chem_on = false;
   int chem_nT = 0, chem_np = 0;
   std::vector<double> chem_tab, chem_T, chem_logp;   // host copies (frei_kappa)
-  double *d_chem_tab = nullptr, *d_chem_T = nullptr, *d_chem_pz = nullptr;
-  int32_t* d_chem_pj = nullptr;
+  DevBuf<double> d_chem_tab, d_chem_T, d_chem_pz;
+  DevBuf<int32_t> d_chem_pj;
   // batched contexts (frei_set_chemistry_batch): chem_ntab tables, atmosphere m reads table
   // chem_atm[m] (empty: one table for the context, frei_set_chemistry)
   int chem_ntab = 1;
   std::vector<int32_t> chem_atm;
-  int32_t* d_chem_atm = nullptr;
+  DevBuf<int32_t> d_chem_atm;
   // Atmosphere-tiled per-species sweep of a chemistry batch (sweep_tile_kernel): atmospheres
   // per block, FREI_ATM_TILE 1 (one block per (wavelength block, atmosphere): the one-lane
   // per-species sweep), 2, 4 or -1 = automatic; tile: the width the last metadata build chose
@@ -288,22 +288,23 @@ struct frei_ctx {
   std::vector<char> kmix_used;       // [n_p] a layer sits on the row (the last metadata build)
   // P2P exchange over xGMI (frei_comm_p2p_*): own mailbox (uncached device memory), the
   // mapped mailboxes of every rank (own included) and the per-sweep sequence number
-  double* d_mbox = nullptr;
-  double** d_peers = nullptr;
-  std::vector<void*> peer_mapped;        // IPC mappings to close
+  DevBuf<double> d_mbox;                 // (adopted: allocated uncached)
+  DevBuf<double*> d_peers;
+  std::vector<void*> peer_mapped;        // IPC mappings to close (not allocations)
   uint64_t p2p_seq = 0;
-  int* d_comm_err = nullptr;             // set by a kernel when a peer never published
-  unsigned long long* d_wait_ticks = nullptr;
+  DevBuf<int> d_comm_err;                // set by a kernel when a peer never published
+  DevBuf<unsigned long long> d_wait_ticks;
   double p2p_timeout_s = 30.0;           // FREI_P2P_TIMEOUT_S
   frei_allgather_fn host_ag = nullptr;  // host all-gather callback (alternative to RCCL)
   void* host_ag_user = nullptr;
-  double* h_ag = nullptr;               // pinned [nranks + 1][n_steps * 4]
+  PinnedBuf<double> h_ag;               // pinned [nranks + 1][n_steps * 4]
   // timing
   bool timing = false;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<Event> ev_pool;
   size_t ev_used = 0;
-  std::vector<hipEvent_t> xev_pool;     // around the rank exchange (all-gather) of each sweep
+  std::vector<Event> xev_pool;          // around the rank exchange (all-gather) of each sweep
   size_t xev_used = 0;
+  ~frei_ctx();
 };
 
 namespace {
@@ -316,7 +317,7 @@ int set_device(frei_ctx* c) {
 // A setup or per-run upload (never inside the T-P loop) that waits for the copy: the sources are
 // often temporaries (pageable, freed at the caller's scope exit).
 template <typename T>
-int h2d_wait(T* d, const T* h, size_t n, hipStream_t st) {
+int h2d_wait(DevPtr<T> d, const T* h, size_t n, hipStream_t st) {
   TRY(h2d(d, h, n, st));
   HIP_TRY(hipStreamSynchronize(st));
   return 0;
@@ -492,12 +493,9 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   const Species& q0 = c->sp[0];
   const size_t per = (size_t)q0.n_p * q0.n_T * (size_t)q0.stride + 64;
   const size_t need = per * c->n_atm;
-  if (c->eff_cap < need) {
+  if (c->d_eff.capacity() < need) {
     HIP_TRY(hipStreamSynchronize(c->stream));   // no queued sweep still reads the old table
-    dfree(c->d_eff);
-    c->eff_cap = 0;
-    TRY(dalloc(&c->d_eff, need));
-    c->eff_cap = need;
+    TRY(c->d_eff.reserve(need));
   }
   lap(2);
   c->eff_stride = per;
@@ -534,11 +532,10 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   lap(3);
   if (!c->d_ones) {
     std::vector<double> ones(nL, 1.0);
-    TRY(dalloc(&c->d_ones, nL));
+    TRY(c->d_ones.alloc(nL));
     TRY(h2d_wait(c->d_ones, ones.data(), nL, c->stream));
   }
-  dfree(c->d_prow);
-  TRY(dalloc(&c->d_prow, nL));
+  TRY(c->d_prow.reserve(nL));
   TRY(h2d_wait(c->d_prow, prow.data(), nL, c->stream));
   const double* tabs[kMaxFastS];
   for (int s = 0; s < S; ++s) tabs[s] = c->sp[s].d_tab;
@@ -547,8 +544,7 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
   c->lazy_on = c->lazy_k3 && !batch && sweep_plan(c, false, false).form == kLam2;
   c->eff_complete = !c->lazy_on;
   if (c->lazy_on) {
-    dfree(c->d_kvalid);
-    TRY(dalloc(&c->d_kvalid, (size_t)q0.n_p * q0.n_T));
+    TRY(c->d_kvalid.reserve((size_t)q0.n_p * q0.n_T));
     HIP_TRY(hipMemsetAsync(c->d_kvalid, 0, (size_t)q0.n_p * q0.n_T * sizeof(int32_t),
                            c->stream));
     // a layer outside the hull reads rows 0 and 1 with zero weights: finite (zero) until then
@@ -558,21 +554,16 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
     lap(4);
     SpecMeta m = c->smeta[0];
     m.tab = c->d_eff;
-    if (!c->d_smeta_eff) TRY(dalloc(&c->d_smeta_eff, 1));
+    if (!c->d_smeta_eff) TRY(c->d_smeta_eff.alloc(1));
     TRY(h2d_wait(c->d_smeta_eff, &m, 1, c->stream));
     return 0;
   }
-  hipEvent_t k0 = nullptr, k1 = nullptr;   // the contraction kernel alone (frei_contract_timing)
-  if (hipEventCreate(&k0) != hipSuccess || hipEventCreate(&k1) != hipSuccess)
-    return fail("hipEventCreate failed");
+  Event k0, k1;   // the contraction kernel alone (frei_contract_timing)
+  if (k0.create() || k1.create()) return fail("hipEventCreate failed");
   HIP_TRY(hipEventRecord(k0, c->stream));
   if (kmix) {               // K20: K19's random-overlap mixture per atmosphere, not a species sum
     const int rc = kmix_fill(c, 0, c->n_atm, "k-mix batch tables: ");
-    if (rc) {
-      (void)hipEventDestroy(k0);
-      (void)hipEventDestroy(k1);
-      return rc;
-    }
+    if (rc) return rc;
   } else if (batch && c->k7_mfma)  // K7: [n_atm x S] . [S x n_T*pitch] per layer on fp64 MFMA
     launch_contract_batch(tabs, S, c->d_mmr, c->d_prow, nL, q0.n_T, q0.stride, c->n_atm,
                           (int64_t)per, c->d_eff, c->stream);
@@ -597,12 +588,10 @@ int build_contracted(frei_ctx* c, bool shared_fast, Lap&& lap) {
     for (char u : used) rows += u;
     const double rowbytes = (double)q0.n_T * q0.stride * sizeof(double);
     c->contract_bytes = rows * rowbytes * (S + c->n_atm);
-    (void)hipEventDestroy(k0);
-    (void)hipEventDestroy(k1);
   }
   SpecMeta m = c->smeta[0];
   m.tab = c->d_eff;
-  if (!c->d_smeta_eff) TRY(dalloc(&c->d_smeta_eff, 1));
+  if (!c->d_smeta_eff) TRY(c->d_smeta_eff.alloc(1));
   TRY(h2d_wait(c->d_smeta_eff, &m, 1, c->stream));
   return 0;
 }
@@ -729,14 +718,10 @@ int build_meta(frei_ctx* c) {
   c->shared = (c->shared_mode == 1 || (c->shared_mode < 0 && small)) && lds_fits ? shared : 0;
   if (c->tile > 1) c->shared = shared;   // the tiled sweep reads the shared-bracket records
   HIP_TRY(hipStreamSynchronize(c->stream));   // queued kernels may still read the metadata
-  dfree(c->d_smeta);
-  dfree(c->d_pmeta);
-  dfree(c->d_tnodes);
-  dfree(c->d_tperm);
-  TRY(dalloc(&c->d_smeta, S));
-  TRY(dalloc(&c->d_pmeta, (size_t)S * nL));
-  TRY(dalloc(&c->d_tnodes, c->tnodes.size()));
-  TRY(dalloc(&c->d_tperm, c->tperm.size()));
+  TRY(c->d_smeta.reserve(S));
+  TRY(c->d_pmeta.reserve((size_t)S * nL));
+  TRY(c->d_tnodes.reserve(c->tnodes.size()));
+  TRY(c->d_tperm.reserve(c->tperm.size()));
   TRY(h2d_wait(c->d_smeta, c->smeta.data(), S, c->stream));
   TRY(h2d_wait(c->d_pmeta, c->pmeta.data(), (size_t)S * nL, c->stream));
   TRY(h2d_wait(c->d_tnodes, c->tnodes.data(), c->tnodes.size(), c->stream));
@@ -833,11 +818,11 @@ SetupArgs setup_args(const frei_ctx* c) {
   return u;
 }
 
-hipEvent_t next_event_in(std::vector<hipEvent_t>& pool, size_t& used) {
+hipEvent_t next_event_in(std::vector<Event>& pool, size_t& used) {
   if (used == pool.size()) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    pool.push_back(e);
+    Event e;
+    if (e.create()) return nullptr;
+    pool.push_back(std::move(e));
   }
   return pool[used++];
 }
@@ -1247,9 +1232,8 @@ UpdateArgs update_args(frei_ctx* c, const SweepOpts& o, const SweepPlan& p, cons
 int launch_tail(frei_ctx* c, int dir, const SweepPlan& p, FastArgs f, UpdateArgs u) {
   const int64_t need = (int64_t)p.nb_run * (c->nL - 1) * 4;
   if (c->tpart_n < need) {
-    dfree(c->d_tpart);
     c->tpart_n = 0;
-    TRY(dalloc(&c->d_tpart, 2 * (size_t)need));
+    TRY(c->d_tpart.reserve(2 * (size_t)need));
     c->tpart_n = need;
     c->tpart_fill = true;
   }
@@ -1363,8 +1347,8 @@ int reset_loop_state(frei_ctx* c) {
 int ensure_hist(frei_ctx* c, int cap) {
   if (cap <= c->hist_cap) return 0;
   HIP_TRY(hipStreamSynchronize(c->stream));   // queued update kernels may still write it
-  dfree(c->d_hist);
-  TRY(dalloc(&c->d_hist, (size_t)cap * 2 * c->nL * c->n_atm));
+  c->hist_cap = 0;
+  TRY(c->d_hist.reserve((size_t)cap * 2 * c->nL * c->n_atm));
   c->hist_cap = cap;
   return 0;
 }
@@ -1387,7 +1371,7 @@ AtmStride atm_stride(const frei_ctx* c) {
 }
 
 int ensure_dtaus(frei_ctx* c) {
-  if (!c->d_dtaus) TRY(dalloc(&c->d_dtaus, (size_t)c->nL * c->nlam));
+  if (!c->d_dtaus) TRY(c->d_dtaus.alloc((size_t)c->nL * c->nlam));
   launch_fill(c->d_dtaus, c->nlam, 1.0, c->stream);  // row 0 placeholder (Q12)
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1399,15 +1383,9 @@ int ensure_dtaus(frei_ctx* c) {
 int ensure_dtaus_batch(frei_ctx* c) {
   if (c->n_atm == 1) return ensure_dtaus(c);
   const size_t per = (size_t)c->nL * c->nlam, n = per * c->n_atm;
-  if (!c->d_dtaus) {
-    double* p = nullptr;
-    if (hipMalloc((void**)&p, n * sizeof(double)) != hipSuccess) {
-      (void)hipGetLastError();   // not sticky: later launch checks must not see it
-      return fail("cannot allocate " + std::to_string(n * sizeof(double)) + " bytes for " +
-                  std::to_string(c->n_atm) + " atmospheres' dtaus (keep_dtaus)");
-    }
-    c->d_dtaus = p;
-  }
+  if (!c->d_dtaus && c->d_dtaus.alloc(n))   // (no sticky error: alloc cleared it)
+    return fail("cannot allocate " + std::to_string(n * sizeof(double)) + " bytes for " +
+                std::to_string(c->n_atm) + " atmospheres' dtaus (keep_dtaus)");
   launch_fill_rows(c->d_dtaus, c->nlam, (int64_t)per, c->n_atm, 1.0, c->stream);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -1527,6 +1505,30 @@ int ctx_columns(frei_ctx* c, bool need_dtaus, CtxColumns* out) {
 }
 }  // namespace frei
 
+frei_ctx::~frei_ctx() {
+  (void)hipSetDevice(device);
+  if (stream) (void)hipStreamSynchronize(stream);
+  if (comm) {
+    Rccl* r = rccl();
+    if (r && r->commDestroy) r->commDestroy(comm);
+  }
+  if (g_exec) (void)hipGraphExecDestroy(g_exec);
+  for (void* p : peer_mapped) (void)hipIpcCloseMemHandle(p);
+}
+
+// One row of ctx_create's allocation table: a buffer of either kind and its element count
+// (kNone: not for this context).
+constexpr size_t kNone = ~size_t(0);
+struct Want {
+  int (*alloc)(void*, size_t);
+  void* buf;
+  size_t n;
+};
+template <typename T, typename Mem>
+Want want(Buf<T, Mem>& b, size_t n) {
+  return {[](void* p, size_t k) { return static_cast<Buf<T, Mem>*>(p)->alloc(k); }, &b, n};
+}
+
 // ==================================================================== C ABI
 extern "C" {
 
@@ -1537,6 +1539,14 @@ const char* frei_last_error(void) { return g_err.c_str(); }
 int frei_device_count(int* n) {
   if (!n) return fail("null argument");
   HIP_TRY(hipGetDeviceCount(n));
+  return 0;
+}
+
+int frei_live_resources(int64_t* device_buffers, int64_t* pinned_buffers, int64_t* streams,
+                        int64_t* events) {
+  int64_t* const out[4] = {device_buffers, pinned_buffers, streams, events};
+  for (int k = 0; k < 4; ++k)
+    if (out[k]) *out[k] = g_live[k].load();
   return 0;
 }
 
@@ -1564,7 +1574,7 @@ static int ctx_create(frei_ctx** out, int device, int n_layers, int64_t n_lam, i
     if (const char* e = getenv(env.c_str())) (void)set_option(c, *k, atoi(e));
   }
   auto bail = [&](int rc) {
-    frei_ctx_destroy(c);
+    delete c;
     return rc;
   };
   int rc;
@@ -1577,36 +1587,36 @@ static int ctx_create(frei_ctx** out, int device, int n_layers, int64_t n_lam, i
       if (prop.multiProcessorCount > 0) c->n_cu = prop.multiProcessorCount;
     }
   }
-  if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
-    return bail(fail("hipStreamCreate failed"));
+  if (c->stream.create()) return bail(fail("hipStreamCreate failed"));
   const size_t NL = n_layers, NS = n_species, ns = n_layers - 1, A = n_atm;
   const size_t F = NL * (size_t)n_lam * A;   // per-atmosphere buffers are n_atm blocks
-  if ((rc = dalloc(&c->d_c1, n_lam)) || (rc = dalloc(&c->d_hcl, n_lam)) ||
-      (rc = dalloc(&c->d_sig, n_lam)) || (rc = dalloc(&c->d_ftoa, n_lam)) ||
-      (rc = dalloc(&c->d_wtr, n_lam)) || (rc = dalloc(&c->d_p, NL)) || (rc = dalloc(&c->d_lnp, NL)) ||
-      (rc = dalloc(&c->d_Fu, F)) || (rc = dalloc(&c->d_Fd, F)) ||
-      (rc = dalloc(&c->d_T, NL * A)) || (rc = dalloc(&c->d_T_alt, NL * A)) ||
-      (rc = dalloc(&c->d_T3, NL * A)) || (rc = dalloc(&c->d_epoch, NL)) ||
-      (rc = dalloc(&c->d_chain_err, 1)) ||
-      (rc = dalloc(&c->d_done, 1)) || (rc = dalloc(&c->d_dT, NL * A)) ||
-      (rc = dalloc(&c->d_bol, NL * 4 * A)) || (rc = dalloc(&c->d_mmr, NS * NL * A)) ||
-      (rc = dalloc(&c->d_steps, ns * A)) || (rc = dalloc(&c->d_terms, ns * NS * A)) ||
-      (rc = dalloc(&c->d_fsteps, ns * A)) || (rc = dalloc(&c->d_ssteps, ns * A)) ||
-      (rc = dalloc(&c->d_part, ns * 4 * (size_t)(4 * c->nblocks) * A)) ||
-      (rc = dalloc(&c->d_Fb, ns * 4 * A)) || (rc = dalloc(&c->d_Fb_all, ns * 4)) ||
-      (rc = dalloc(&c->d_conv, A)) || (rc = dalloc(&c->d_iter, A)) ||
-      (rc = dalloc(&c->d_Tb, NL * A)) || (rc = dalloc(&c->d_Ta, NL * A)) ||
-      (rc = dalloc(&c->d_flips, NL * A)) || (rc = dalloc(&c->d_prev, NL * A)) ||
-      (rc = dalloc(&c->d_ndiff, NL * A)) || (A > 1 && (rc = dalloc(&c->d_g, A))))
-    return bail(rc);
-  c->d_T_home = c->d_T;
-  if (hipHostMalloc((void**)&c->h_flag, 2 * sizeof(int)) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_err, 2 * sizeof(int)) != hipSuccess)
-    return bail(fail("hipHostMalloc failed"));
+  // every buffer a context starts with and its element count (the others grow on demand)
+  const Want device_bufs[] = {
+      want(c->d_c1, n_lam), want(c->d_hcl, n_lam), want(c->d_sig, n_lam), want(c->d_ftoa, n_lam),
+      want(c->d_wtr, n_lam), want(c->d_p, NL), want(c->d_lnp, NL), want(c->d_Fu, F),
+      want(c->d_Fd, F), want(c->T_buf[0], NL * A), want(c->T_buf[1], NL * A),
+      want(c->T_buf[2], NL * A), want(c->d_epoch, NL), want(c->d_chain_err, 1),
+      want(c->d_done, 1), want(c->d_dT, NL * A), want(c->d_bol, NL * 4 * A),
+      want(c->d_mmr, NS * NL * A), want(c->d_steps, ns * A), want(c->d_terms, ns * NS * A),
+      want(c->d_fsteps, ns * A), want(c->d_ssteps, ns * A),
+      want(c->d_part, ns * 4 * (size_t)(4 * c->nblocks) * A), want(c->d_Fb, ns * 4 * A),
+      want(c->d_Fb_all, ns * 4), want(c->d_conv, A), want(c->d_iter, A), want(c->d_Tb, NL * A),
+      want(c->d_Ta, NL * A), want(c->d_flips, NL * A), want(c->d_prev, NL * A),
+      want(c->d_ndiff, NL * A), want(c->d_g, A > 1 ? A : kNone)};
+  const Want pinned_bufs[] = {
+      want(c->h_flag, 2), want(c->h_err, 2), want(c->h_conv, A > 1 ? 2 * A : kNone),
+      want(c->h_T, NL * A), want(c->h_dT, NL), want(c->h_bol, NL * 4), want(c->h_mmr, NS * NL * A)};
+  for (const Want& w : device_bufs)
+    if (w.n != kNone && (rc = w.alloc(w.buf, w.n))) return bail(rc);
+  for (const Want& w : pinned_bufs)
+    if (w.n != kNone && w.alloc(w.buf, w.n)) return bail(fail("hipHostMalloc failed"));
+  c->d_T = c->d_T_home = c->T_buf[0];
+  c->d_T_alt = c->T_buf[1];
+  c->d_T3 = c->T_buf[2];
   c->h_err[0] = c->h_err[1] = 0;
-  for (int k = 0; k < 2; ++k)
-    if (hipEventCreateWithFlags(&c->flag_ev[k], hipEventDisableTiming) != hipSuccess)
-      return bail(fail("hipEventCreate failed"));
+  if (c->flag_ev[0].create(hipEventDisableTiming) || c->flag_ev[1].create(hipEventDisableTiming) ||
+      c->mmr_ev.create(hipEventDisableTiming))
+    return bail(fail("hipEventCreate failed"));
   // stream-ordered (the context's stream does not synchronise with the null stream)
   if (hipMemsetAsync(c->d_Fu, 0, F * sizeof(double), c->stream) != hipSuccess ||
       hipMemsetAsync(c->d_Fd, 0, F * sizeof(double), c->stream) != hipSuccess ||
@@ -1616,14 +1626,6 @@ static int ctx_create(frei_ctx** out, int device, int n_layers, int64_t n_lam, i
       hipMemsetAsync(c->d_chain_err, 0, sizeof(int), c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return bail(fail("hipMemsetAsync failed"));
-  if (A > 1 && hipHostMalloc((void**)&c->h_conv, 2 * A * sizeof(int)) != hipSuccess)
-    return bail(fail("hipHostMalloc failed"));
-  if (hipHostMalloc((void**)&c->h_T, NL * A * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_dT, NL * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_bol, NL * 4 * sizeof(double)) != hipSuccess ||
-      hipHostMalloc((void**)&c->h_mmr, (size_t)n_species * NL * A * sizeof(double)) != hipSuccess ||
-      hipEventCreateWithFlags(&c->mmr_ev, hipEventDisableTiming) != hipSuccess)
-    return bail(fail("hipHostMalloc failed"));
   *out = c;
   return 0;
 }
@@ -1640,59 +1642,7 @@ int frei_ctx_create_batch(frei_ctx** out, int device, int n_layers, int64_t n_la
 }
 
 int frei_ctx_destroy(frei_ctx* c) {
-  if (!c) return 0;
-  (void)hipSetDevice(c->device);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->comm) {
-    Rccl* r = rccl();
-    if (r && r->commDestroy) r->commDestroy(c->comm);
-  }
-  if (c->g_exec) (void)hipGraphExecDestroy(c->g_exec);
-  c->g_exec = nullptr;
-  for (void* p : c->peer_mapped) (void)hipIpcCloseMemHandle(p);
-  c->peer_mapped.clear();
-  dfree(c->d_peers);
-  dfree(c->d_mbox);
-  dfree(c->d_comm_err);
-  dfree(c->d_wait_ticks);
-  dfree(c->d_epoch);
-  dfree(c->d_chain_err);
-  dfree(c->d_tpart);
-  dfree(c->d_kvalid);
-  for (auto& s : c->sp) dfree(s.d_tab);
-  dfree(c->d_eff);
-  dfree(c->d_smeta_eff);
-  dfree(c->d_chem_tab);
-  dfree(c->d_chem_T);
-  dfree(c->d_chem_pz);
-  dfree(c->d_chem_pj);
-  dfree(c->d_chem_atm);
-  dfree(c->d_ones);
-  dfree(c->d_prow);
-  double* dd[] = {c->d_c1, c->d_hcl, c->d_sig, c->d_ftoa, c->d_wtr, c->d_p, c->d_lnp,
-                  c->d_Fu, c->d_Fd, c->d_T, c->d_T_alt, c->d_T3, c->d_dT, c->d_dtaus, c->d_bol, c->d_tnodes, c->d_mmr, c->d_part,
-                  c->d_Fb, c->d_Fb_all, c->d_Tb, c->d_Ta, c->d_hist};
-  for (double* p : dd)
-    if (p) (void)hipFree(p);
-  void* vv[] = {c->d_smeta, c->d_pmeta, c->d_tperm, c->d_steps, c->d_terms, c->d_fsteps,
-                c->d_ssteps, c->d_conv, c->d_iter, c->d_flips, c->d_prev, c->d_ndiff,
-                c->d_done};
-  for (void* p : vv)
-    if (p) (void)hipFree(p);
-  if (c->h_flag) (void)hipHostFree(c->h_flag);
-  if (c->h_err) (void)hipHostFree(c->h_err);
-  if (c->h_conv) (void)hipHostFree(c->h_conv);
-  for (double* h : {c->h_T, c->h_dT, c->h_bol, c->h_mmr})
-    if (h) (void)hipHostFree(h);
-  if (c->mmr_ev) (void)hipEventDestroy(c->mmr_ev);
-  dfree(c->d_g);
-  if (c->h_ag) (void)hipHostFree(c->h_ag);
-  for (auto e : c->flag_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto e : c->xev_pool) (void)hipEventDestroy(e);
-  for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+  if (c) delete c;
   return 0;
 }
 
@@ -1758,8 +1708,7 @@ static int set_table_common(frei_ctx* c, int s, const double* p_nodes, int n_p,
   // queued sweeps of the old tables must finish before they are overwritten or freed
   HIP_TRY(hipStreamSynchronize(c->stream));
   if (!q.d_tab || (size_t)q.n_p * q.n_T != (size_t)n_p * n_T) {
-    dfree(q.d_tab);
-    TRY(dalloc(&q.d_tab, need));
+    TRY(q.d_tab.alloc(need));
   }
   // finite padding; on the context's stream, ordered before the table upload / generation.
   // (A null-stream hipMemset is not ordered with the non-blocking stream: it could still be
@@ -2016,8 +1965,7 @@ int frei_set_ftoa_batch(frei_ctx* c, const double* f_toa) {
   double* d = call.upload(f_toa, n);
   call.keep(d);
   TRY(call.finish());   // (queued sweeps have finished with the old F_TOA too)
-  dfree(c->d_ftoa);
-  c->d_ftoa = d;
+  c->d_ftoa.adopt(d, n);
   c->ftoa_per_atm = true;
   return 0;
 }
@@ -2043,16 +1991,12 @@ static int set_chem_tables(frei_ctx* c, const double* values, int n_tab, const i
   std::vector<double> pz(nL);
   for (int l = 0; l < nL; ++l)   // layer pressures are fixed: their log10 p brackets once
     chem_bracket(c->chem_logp.data(), n_p, std::log10(c->p[l]), pj[l], pz[l]);
-  dfree(c->d_chem_tab);
-  dfree(c->d_chem_T);
-  dfree(c->d_chem_pj);
-  dfree(c->d_chem_pz);
-  dfree(c->d_chem_atm);
+  c->d_chem_atm.reset();
   c->chem_on = false;
-  TRY(dalloc(&c->d_chem_tab, nv));
-  TRY(dalloc(&c->d_chem_T, n_T));
-  TRY(dalloc(&c->d_chem_pj, nL));
-  TRY(dalloc(&c->d_chem_pz, nL));
+  TRY(c->d_chem_tab.alloc(nv));
+  TRY(c->d_chem_T.alloc(n_T));
+  TRY(c->d_chem_pj.alloc(nL));
+  TRY(c->d_chem_pz.alloc(nL));
   TRY(h2d_wait(c->d_chem_tab, c->chem_tab.data(), nv, c->stream));
   TRY(h2d_wait(c->d_chem_T, c->chem_T.data(), n_T, c->stream));
   TRY(h2d_wait(c->d_chem_pj, pj.data(), nL, c->stream));
@@ -2060,7 +2004,7 @@ static int set_chem_tables(frei_ctx* c, const double* values, int n_tab, const i
   c->chem_atm.clear();
   if (atm_tab) {
     c->chem_atm.assign(atm_tab, atm_tab + c->n_atm);
-    TRY(dalloc(&c->d_chem_atm, c->n_atm));
+    TRY(c->d_chem_atm.alloc(c->n_atm));
     TRY(h2d_wait(c->d_chem_atm, c->chem_atm.data(), c->n_atm, c->stream));
   }
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2551,18 +2495,16 @@ int frei_kappa(frei_ctx* c, double T, double p, double* k, double* sigma) {
     }
     terms[s] = make_term(sm, pm, c->tnodes.data(), c->tperm.data(), m, T, 0);
   }
-  TermP* d_terms = nullptr;
-  double* d_k = nullptr;
-  TRY(dalloc(&d_terms, c->S));
-  TRY(dalloc(&d_k, c->nlam));
+  DevBuf<TermP> d_terms;
+  DevBuf<double> d_k;
+  TRY(d_terms.alloc(c->S));
+  TRY(d_k.alloc(c->nlam));
   TRY(h2d_wait(d_terms, terms.data(), c->S, c->stream));
   launch_kappa(c->nlam, d_terms, c->S, c->d_sig, d_k, c->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(c->stream));
   HIP_TRY(hipMemcpy(k, d_k, c->nlam * sizeof(double), hipMemcpyDeviceToHost));
   if (sigma) HIP_TRY(hipMemcpy(sigma, c->d_sig, c->nlam * sizeof(double), hipMemcpyDeviceToHost));
-  dfree(d_terms);
-  dfree(d_k);
   return 0;
 }
 
@@ -2577,15 +2519,14 @@ int frei_propagate_fluxes(int device, int64_t n, const double* c1, const double*
   // inputs c1, lk, F_1_up, F_2_down, delta_tau, omega_0 [, g_0]; outputs F_2_up, F_1_down
   const double* in[7] = {c1, lk, F_1_up, F_2_down, delta_tau, omega_0, g_0};
   const int n_in = g_0 ? 7 : 6;
-  double* d[9] = {};
-  hipStream_t st = nullptr;
+  Stream st;   // (before the buffers: destroyed after them)
+  DevBuf<double> d[9];
   int rc = 0;
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess)
-    return fail("hipStreamCreate failed");
-  for (int i = 0; i < n_in + 2 && !rc; ++i) rc = dalloc(&d[i], n);
+  if (st.create()) return fail("hipStreamCreate failed");
+  for (int i = 0; i < n_in + 2 && !rc; ++i) rc = d[i].alloc(n);
   for (int i = 0; i < n_in && !rc; ++i) rc = h2d_wait(d[i], in[i], n, st);
   if (!rc) {
-    launch_propagate(n, d[0], d[1], d[2], d[3], T_1, T_2, d[4], d[5], g_0 ? d[6] : nullptr,
+    launch_propagate(n, d[0], d[1], d[2], d[3], T_1, T_2, d[4], d[5], g_0 ? d[6].get() : nullptr,
                      d[n_in], d[n_in + 1], st);
     if (hipGetLastError() != hipSuccess) rc = fail("propagate kernel launch failed");
   }
@@ -2595,8 +2536,6 @@ int frei_propagate_fluxes(int device, int64_t n, const double* c1, const double*
                              st) != hipSuccess))
     rc = fail("propagate copy failed");
   if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = fail("propagate kernel failed");
-  for (double*& p : d) dfree(p);
-  (void)hipStreamDestroy(st);
   return rc;
 }
 
@@ -2632,8 +2571,7 @@ int frei_comm_init(frei_ctx* c, int nranks, int rank, const void* id128) {
   c->comm = comm;
   c->nranks = nranks;
   c->rank = rank;
-  dfree(c->d_Fb_all);
-  TRY(dalloc(&c->d_Fb_all, (size_t)nranks * (c->nL - 1) * 4));
+  TRY(c->d_Fb_all.alloc((size_t)nranks * (c->nL - 1) * 4));
   return 0;
 }
 
@@ -2644,12 +2582,8 @@ int frei_comm_init_host(frei_ctx* c, int nranks, int rank, frei_allgather_fn fn,
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail("bad rank/nranks");
   TRY(set_device(c));
   const size_t n = (size_t)(c->nL - 1) * 4;
-  if (c->h_ag) (void)hipHostFree(c->h_ag);
-  c->h_ag = nullptr;
-  if (hipHostMalloc((void**)&c->h_ag, (nranks + 1) * n * sizeof(double)) != hipSuccess)
-    return fail("hipHostMalloc failed");
-  dfree(c->d_Fb_all);
-  TRY(dalloc(&c->d_Fb_all, (size_t)nranks * n));
+  if (c->h_ag.alloc((nranks + 1) * n)) return fail("hipHostMalloc failed");
+  TRY(c->d_Fb_all.alloc((size_t)nranks * n));
   c->host_ag = fn;
   c->host_ag_user = user;
   c->nranks = nranks;
@@ -2668,7 +2602,7 @@ int frei_comm_p2p_handle(frei_ctx* c, int nranks, int rank, void* handle64) {
   const int64_t n = (int64_t)(c->nL - 1) * 4;
   void* mb = nullptr;
   HIP_TRY(hipExtMallocWithFlags(&mb, mbox_bytes(nranks, n), hipDeviceMallocUncached));
-  c->d_mbox = static_cast<double*>(mb);
+  c->d_mbox.adopt(static_cast<double*>(mb), mbox_bytes(nranks, n) / sizeof(double));
   // flags 0: nothing published; complete before the handle goes to the peers
   HIP_TRY(hipMemsetAsync(c->d_mbox, 0, mbox_bytes(nranks, n), c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
@@ -2700,14 +2634,13 @@ int frei_comm_p2p_open(frei_ctx* c, const void* handles) {
     c->peer_mapped.push_back(p);
     ptr[r] = static_cast<double*>(p);
   }
-  TRY(dalloc(&c->d_peers, R));
+  TRY(c->d_peers.alloc(R));
   TRY(h2d_wait(c->d_peers, ptr.data(), R, c->stream));
-  TRY(dalloc(&c->d_comm_err, 1));
-  TRY(dalloc(&c->d_wait_ticks, 1));
+  TRY(c->d_comm_err.alloc(1));
+  TRY(c->d_wait_ticks.alloc(1));
   HIP_TRY(hipMemsetAsync(c->d_comm_err, 0, sizeof(int), c->stream));
   HIP_TRY(hipMemsetAsync(c->d_wait_ticks, 0, sizeof(unsigned long long), c->stream));
-  dfree(c->d_Fb_all);
-  TRY(dalloc(&c->d_Fb_all, (size_t)R * (c->nL - 1) * 4));
+  TRY(c->d_Fb_all.alloc((size_t)R * (c->nL - 1) * 4));
   // handshake: every rank publishes flag 1 in every mailbox and waits for all (bounded)
   P2PPush push{};
   push.peers = c->d_peers;

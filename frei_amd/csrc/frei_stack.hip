@@ -34,16 +34,21 @@
 using namespace frei;
 
 struct frei_stack {
+  Stream stream;   // first: destroyed last; created by the first apply, before any buffer
   int device = 0;
-  hipStream_t stream = nullptr;
   int n_exp = 0, n_vel = 0, n_kp = 0, n_vsys = 0;
   // the host copies frei_stack_create checked; uploaded by the first apply
   std::vector<double> vel, dv, v_obs, vsys;
   bool resident = false;
-  double* d_vel = nullptr;    // [n_vel]
-  double* d_dv = nullptr;     // [n_kp][n_exp]
-  double* d_vobs = nullptr;   // [n_exp]
-  double* d_vsys = nullptr;   // [n_vsys]
+  DevBuf<double> d_vel;    // [n_vel]
+  DevBuf<double> d_dv;     // [n_kp][n_exp]
+  DevBuf<double> d_vobs;   // [n_exp]
+  DevBuf<double> d_vsys;   // [n_vsys]
+  ~frei_stack() {
+    if (!stream) return;   // no device was touched
+    (void)hipSetDevice(device);
+    (void)hipStreamSynchronize(stream);
+  }
 };
 
 namespace {
@@ -162,16 +167,16 @@ int check_finite(const char* name, const double* x, int64_t n, int64_t cols) {
 int make_resident(frei_stack* s) {
   if (s->resident) return 0;
   HIP_TRY(hipSetDevice(s->device));
-  if (!s->stream) HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-  auto up = [&](double** d, const std::vector<double>& h) {
-    if (!*d) TRY(dalloc(d, h.size()));
-    HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+  if (!s->stream) TRY(s->stream.create());
+  auto up = [&](DevBuf<double>& d, const std::vector<double>& h) {
+    if (!d) TRY(d.alloc(h.size()));
+    HIP_TRY(hipMemcpy(d, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
     return 0;
   };
-  TRY(up(&s->d_vel, s->vel));
-  TRY(up(&s->d_dv, s->dv));
-  TRY(up(&s->d_vobs, s->v_obs));
-  TRY(up(&s->d_vsys, s->vsys));
+  TRY(up(s->d_vel, s->vel));
+  TRY(up(s->d_dv, s->dv));
+  TRY(up(s->d_vobs, s->v_obs));
+  TRY(up(s->d_vsys, s->vsys));
   s->resident = true;
   return 0;
 }
@@ -216,17 +221,7 @@ int frei_stack_create(frei_stack** out, int device, int n_exp, int n_vel, const 
 }
 
 int frei_stack_destroy(frei_stack* s) {
-  if (!s) return 0;
-  if (s->stream || s->d_vel || s->d_dv || s->d_vobs || s->d_vsys) {
-    (void)hipSetDevice(s->device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    dfree(s->d_vel);
-    dfree(s->d_dv);
-    dfree(s->d_vobs);
-    dfree(s->d_vsys);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-  }
-  delete s;
+  if (s) delete s;
   return 0;
 }
 

@@ -28,17 +28,19 @@
 using namespace frei;
 
 struct frei_sspec {
+  Stream stream;   // first: destroyed last
   int device = 0;
-  hipStream_t stream = nullptr;
   int n_spec = 0;
   int64_t nhi = 0;
   std::vector<double> wl;     // µm, strictly ascending
-  double* d_flux = nullptr;   // [n_spec][nhi]
-  double* d_wl = nullptr;     // [nhi]
-  int64_t* d_pos = nullptr;   // [n_bins + 1] plan of the last call (kept between calls)
-  size_t pos_cap = 0;
-  double* d_out = nullptr;    // [n_spec][n_bins] result of the last call
-  size_t out_cap = 0;
+  DevBuf<double> d_flux;   // [n_spec][nhi]
+  DevBuf<double> d_wl;     // [nhi]
+  DevBuf<int64_t> d_pos;   // [n_bins + 1] plan of the last call (kept between calls, grow-only)
+  DevBuf<double> d_out;    // [n_spec][n_bins] result of the last call (grow-only)
+  ~frei_sspec() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
 };
 
 namespace {
@@ -171,17 +173,6 @@ int wave_group(double mean_points) {
 #endif
 }
 
-template <typename T>
-int grow(T** p, size_t* cap, size_t n) {
-  if (*cap >= n) return 0;
-  if (*p) (void)hipFree((void*)*p);
-  *p = nullptr;
-  *cap = 0;
-  HIP_TRY(hipMalloc((void**)p, n * sizeof(T)));
-  *cap = n;
-  return 0;
-}
-
 }  // namespace
 
 // ==================================================================== C ABI
@@ -200,18 +191,16 @@ int frei_sspec_create(frei_sspec** out, int device, const double* flux, int n_sp
   s->nhi = n_hi;
   s->wl.assign(wl_hi, wl_hi + n_hi);
   const size_t nflux = (size_t)n_spec * n_hi;
-  if (hipSetDevice(device) != hipSuccess ||
-      hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void**)&s->d_flux, nflux * sizeof(double)) != hipSuccess ||
-      hipMalloc((void**)&s->d_wl, (size_t)n_hi * sizeof(double)) != hipSuccess) {
-    frei_sspec_destroy(s);
+  if (hipSetDevice(device) != hipSuccess || s->stream.create() || s->d_flux.alloc(nflux) ||
+      s->d_wl.alloc((size_t)n_hi)) {
+    delete s;
     (void)hipGetLastError();
     return set_error("frei_sspec_create: device allocation failed");
   }
   if (hipMemcpy(s->d_flux, flux, nflux * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(s->d_wl, wl_hi, (size_t)n_hi * sizeof(double), hipMemcpyHostToDevice) !=
           hipSuccess) {
-    frei_sspec_destroy(s);
+    delete s;
     (void)hipGetLastError();
     return set_error("frei_sspec_create: host-to-device copy failed");
   }
@@ -220,15 +209,7 @@ int frei_sspec_create(frei_sspec** out, int device, const double* flux, int n_sp
 }
 
 int frei_sspec_destroy(frei_sspec* s) {
-  if (!s) return 0;
-  (void)hipSetDevice(s->device);
-  if (s->stream) (void)hipStreamSynchronize(s->stream);
-  if (s->d_flux) (void)hipFree(s->d_flux);
-  if (s->d_wl) (void)hipFree(s->d_wl);
-  if (s->d_pos) (void)hipFree(s->d_pos);
-  if (s->d_out) (void)hipFree(s->d_out);
-  if (s->stream) (void)hipStreamDestroy(s->stream);
-  delete s;
+  if (s) delete s;
   return 0;
 }
 
@@ -262,8 +243,8 @@ int frei_sspec_bin(frei_sspec* s, const double* wl_bins, int64_t n_bins, int for
   const size_t total = (size_t)s->n_spec * n_bins;
   // d_pos and d_out are the handle's, kept between calls: the call owns nothing
   DeviceCall call(st, "stellar binning");
-  call.check(grow(&s->d_pos, &s->pos_cap, pos.size()));
-  if (call.ok()) call.check(grow(&s->d_out, &s->out_cap, total));
+  call.check(s->d_pos.reserve(pos.size()));
+  if (call.ok()) call.check(s->d_out.reserve(total));
   call.copy_in(s->d_pos, pos.data(), pos.size());
   call.begin(kernel_ms);
   if (call.ok()) {

@@ -49,6 +49,14 @@ int frei_version(void);
 const char* frei_last_error(void);
 /* Number of visible HIP devices. */
 int frei_device_count(int* n);
+/*
+ * What this process's handles hold right now: device buffers, pinned host buffers, streams
+ * and events (a null pointer skips that figure).  Every handle type owns its resources
+ * through the same counted types, so the figures return to their earlier values when a handle
+ * is destroyed and a call's temporaries do not outlive the call.  Needs no device and no handle.
+ */
+int frei_live_resources(int64_t* device_buffers, int64_t* pinned_buffers, int64_t* streams,
+                        int64_t* events);
 
 /* Context for n_layers x n_lam (local slice) x n_species on `device`. */
 int frei_ctx_create(frei_ctx** out, int device, int n_layers, int64_t n_lam, int n_species);
